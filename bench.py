@@ -15,14 +15,23 @@ value = RHS evaluations per second over the whole job, inputs resident in HBM.
 Multi-GPU (one process per GPU, RCCL): by default ONE shared graph, strong
 scaling.  The headline is G-arxiv in feature-column stripes
 (gnpde.dist.ColumnShardedLaplacian: replicated CSR, C/N columns per rank, no
-per-RHS collective); every line also carries the configs[4] graph (G-rmat:
+per-RHS collective); under --full the line also carries the configs[4] graph (G-rmat:
 N = 2M, E = 20M, C = 256) in column stripes and in the north star's literal
 row partition (nnz-balanced blocks + an RCCL all-gather of the state before
 every RHS), each with the same graph timed unsharded on one GPU of the same
 job ("speedup_vs_1gpu").  --mode replicas keeps the old independent-graph
 weak-scaling layout.
 
-Extra objects on the JSON line:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the headline line (metric / value / unit / ms_per_step and
+the K1 roofline taken from the events of the timed steps themselves).  Every
+other measurement below takes runs of its own and is made only under --full
+(the --no-* options then leave single legs out).  --dump-outputs DIR writes the
+state the last timed step returned as DIR/y.npy (float32; a fixed seeded sample
+of its rows when the state is larger than 48 MiB): graph and features are
+seeded, so two builds run with the same arguments can be compared row for row.
+
+Extra objects on the JSON line (--full, except roofline):
   roofline      K1: measured HBM bytes per launch (PMC 2*FETCH_SIZE + WRITE_SIZE,
                 profiles/k1_traffic.json) over the mean launch time from HIP
                 events on the launch stream, vs 8 TB/s; the SURVEY §8(d)
@@ -94,6 +103,11 @@ def parse():
     p.add_argument("--edges", type=int, default=1200000)
     p.add_argument("--dim", type=int, default=128)
     p.add_argument("--step-size", type=float, default=0.25)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also measure every secondary leg (plain-RHS roofline, attention, BLEND, "
+                        "dopri5, training steps, G-rmat, CPU baselines); the --no-* options leave legs out of it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the state the last timed step returned as DIR/<name>.npy (float32)")
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU-baseline sample")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-attention", action="store_true")
@@ -106,7 +120,34 @@ def parse():
                    help="multi-GPU layout of the headline: auto = cols for N > 1; cols / rows = one shared graph "
                         "(column stripes / row partition + all-gather per RHS, strong scaling); replicas = an "
                         "independent graph per rank (weak scaling)")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run measures the headline and nothing else
+        args.no_cpu_baseline = args.no_attention = args.no_train = args.no_grmat = True
+        args.rhs_plain_reps = 0
+    return args
+
+
+DUMP_MAX_BYTES = 48 << 20  # of all the arrays of one --dump-outputs together (every rank's)
+
+
+def dump_outputs(path, arrays, parts=1):
+    """--dump-outputs: every tensor of `arrays` as path/<name>.npy, float32 (a
+    float64 tensor stays float64).  An array over its share of DUMP_MAX_BYTES is
+    written as a sample of its rows ([..., C] seen as [rows, C]): the same rows
+    in every run (numpy default_rng(0), ascending), so two runs with the same
+    arguments write comparable files.  parts: how many ranks write into path."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays) * parts, 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        rows = t.reshape(-1, t.shape[-1])
+        keep = share // (rows.shape[1] * rows.element_size())
+        if rows.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))
+            t = rows[torch.from_numpy(idx).to(rows.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 LAP_OPT = {'block': 'constant', 'function': 'laplacian', 'add_source': False, 'no_alpha_sigmoid': False,
@@ -249,6 +290,8 @@ def bench_single(args, world, rank, dev):
         ops.spmm_rhs = fld.ops.spmm_rhs = orig_spmm
         integ.replay_events = None
     assert torch.isfinite(y).all()
+    if args.dump_outputs:  # the state the timed solve returned, before anything else runs
+        dump_outputs(args.dump_outputs, {"y" if world == 1 else "y_rank%d" % rank: y}, world)
     # per-RHS launch time: eager launches are bracketed one by one; a replayed
     # step (4 K1 launches, hub rows combined inside them, nothing else) is bracketed whole
     t_ev = sum(s.elapsed_time(e) for s, e in events) + sum(s.elapsed_time(e) for s, e, _ in replays)
@@ -454,7 +497,7 @@ def bench_sharded(args, world, rank, dev, mode):
         import random
         dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % random.randint(20000, 40000), rank=0,
                                 world_size=1, device_id=dev)
-    r = sharded_point(N, E, C, h, args.steps, args.warmup, world, dev, mode)
+    r = sharded_point(N, E, C, h, args.steps, args.warmup, world, dev, mode, dump=args.dump_outputs)
     return {
         "metric": METRIC, "value": r["value"], "unit": "RHS evals/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "strong",
@@ -477,9 +520,10 @@ def progress(*a):
 T_START = time.perf_counter()
 
 
-def sharded_point(N, E, C, h, steps, warmup, world, dev, mode, seed=0):
+def sharded_point(N, E, C, h, steps, warmup, world, dev, mode, seed=0, dump=None):
     """RHS evals/s of one graph in `mode` over the job's ranks, and the same graph
-    integrated unsharded on one GPU (every rank at once, max over ranks)."""
+    integrated unsharded on one GPU (every rank at once, max over ranks).  dump:
+    a directory for this rank's shard of the sharded solve's result (dump_outputs)."""
     import gnpde
     from gnpde import dist as gd, synthetic
     progress("sharded point: N=%d E=%d C=%d mode=%s world=%d" % (N, E, C, mode, world))
@@ -502,6 +546,8 @@ def sharded_point(N, E, C, h, steps, warmup, world, dev, mode, seed=0):
         y0 = sh.split(x)
         info = {"columns_per_rank": sh.c1 - sh.c0}
     el, y = timed_solve(sh, y0, steps, warmup, h, dev, world)
+    if dump:
+        dump_outputs(dump, {"y_%s_rank%d" % (mode, dist.get_rank()): y}, world)
     progress("%s: %.3f ms per step" % (mode, el * 1e3 / steps))
     if mode == "rows":
         rp = sh.g.csr.rowptr.cpu()

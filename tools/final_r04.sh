@@ -11,5 +11,5 @@ timeout -k 10 600 python3 -u -m pytest tests -m gpu -q --timeout 120 --timeout-m
 rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest.log; [ $rc = 0 ] || exit $rc
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 $OUT/smoke.log; [ $rc = 0 ] || exit $rc
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; tail -c 400 $OUT/bench.json; [ $rc = 0 ] || exit $rc

@@ -14,6 +14,6 @@ timeout -k 10 300 python3 -c 'import __graft_entry__ as g; g.smoke()' > $OUT/smo
 echo "smoke rc=$rc"; tail -3 $OUT/smoke.log
 [ $rc = 0 ] || exit $rc
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.log 2>&1; rc=$?
+  timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -c 1500 $OUT/bench.log
 fi

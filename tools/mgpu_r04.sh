@@ -17,8 +17,8 @@ run() {  # name, port, args...
   echo "$name rc=$rc"; grep -h '^{' $OUT/$name.log | cut -c1-1500
   [ $rc = 0 ] || exit $rc
 }
-run attn_cols 29527 bench.py --gpus 1 --mode cols --steps 10 --warmup 2 --no-grmat --no-cpu-baseline --no-train
-run attn_rows 29528 bench.py --gpus 1 --mode rows --steps 10 --warmup 2 --no-grmat --no-cpu-baseline --no-train
+run attn_cols 29527 bench.py --full --gpus 1 --mode cols --steps 10 --warmup 2 --no-grmat --no-cpu-baseline --no-train
+run attn_rows 29528 bench.py --full --gpus 1 --mode rows --steps 10 --warmup 2 --no-grmat --no-cpu-baseline --no-train
 run grmat_cols 29529 bench.py --gpus 1 --mode cols --nodes 2000000 --edges 20000000 --dim 256 --steps 10 --warmup 2 \
   --no-grmat --no-cpu-baseline --no-attention --no-train
 run grmat_rows 29530 bench.py --gpus 1 --mode rows --nodes 2000000 --edges 20000000 --dim 256 --steps 10 --warmup 2 \

@@ -33,7 +33,7 @@ if [[ " $STEPS " == *" pmc "* ]]; then
 fi
 if [[ " $STEPS " == *" trace "* ]]; then
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-    python3 $R/bench.py --no-cpu-baseline > $OUT/trace.log 2>&1
+    python3 $R/bench.py --full --no-cpu-baseline > $OUT/trace.log 2>&1
   rc=$?; echo "trace rc=$rc"; tail -c 300 $OUT/trace.log; echo; if fatal $rc; then exit $rc; fi
   # keep the per-kernel stats and a summary; the full trace is too large to merge back
   t=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
@@ -44,6 +44,6 @@ if [[ " $STEPS " == *" trace "* ]]; then
 fi
 if [[ " $STEPS " == *" bench "* ]]; then
   cd $R
-  timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.log 2>&1; rc=$?
+  timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -c 600 $OUT/bench.log
 fi

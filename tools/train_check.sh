@@ -13,5 +13,5 @@ echo "pytest rc=$rc"; tail -3 $OUT/pytest.log
 [ $rc = 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-  python3 $R/bench.py --steps 20 --warmup 5 --no-grmat --no-cpu-baseline --no-attention > $OUT/bench.log 2>&1
+  python3 $R/bench.py --full --steps 20 --warmup 5 --no-grmat --no-cpu-baseline --no-attention > $OUT/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -c 300 $OUT/bench.log
