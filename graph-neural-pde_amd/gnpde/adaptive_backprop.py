@@ -12,7 +12,7 @@ per-RHS autograd nodes: ~175 us of host work per RHS on a Cora-sized graph.
 
 Here (the Laplacian f(y) = L y + s, L = sigma(alpha)(A(w) - I), s = beta x0):
 
-forward  — the tableau's stage plan (integrator._AdaptivePlan) with every combination and
+forward  — the tableau's stage plan (solver_common._AdaptivePlan) with every combination and
            the error rows in the K1 epilogues, each accepted step's stage inputs kept
            (Yin_i, i < ns), torchdiffeq's controller on the host (one read per step);
 backward — per accepted step, last first, the transposed stages (gather form):
@@ -37,16 +37,17 @@ import math
 import torch
 
 from . import ops
+from .solver_common import _adaptive_plan, alpha_grad, check_step, dense_weights, next_dt, rotate
 
 
 class AdaptiveBackprop(object):
-    """One solve: ``forward()`` -> solution; ``backward(grad_sol)`` -> (ybar, alpha, beta, w grads)."""
+    """One solve: ``forward()`` -> solution; ``backward(grad_sol, operands, w)`` -> (ybar, alpha,
+    beta, w grads), reading the module's state only as the LaplacianOperands snapshot the caller
+    took in forward (integrator._LaplacianAdaptiveFn)."""
 
     def __init__(self, func, y0, t_h, method, rtol, atol, first_step=None, max_num_steps=2 ** 31 - 1):
-        from . import integrator as gi
-        self.gi = gi
         self.func, self.y0, self.t_h = func, y0.contiguous(), list(t_h)
-        self.plan = gi._adaptive_plan(method)
+        self.plan = _adaptive_plan(method)
         self.order = float(self.plan.order)
         self.rtol, self.atol = float(rtol), float(atol)
         self.first_step, self.max_num_steps = first_step, max_num_steps
@@ -73,11 +74,6 @@ class AdaptiveBackprop(object):
         ops.initial_step(y, k0, f1, self.atol, self.rtol, self.order, h, None)
         return float(h[2])
 
-    def _combo(self, spec, bufs, x, dt):
-        base, terms, cfc = spec
-        bt = {'Y': bufs['Y'], 'X': x, 'E': bufs.get('E'), None: None}[base]
-        return bt, (1.0 if bt is not None else 0.0), cfc * dt, [(bufs[k], c * dt) for k, c in terms]
-
     def _attempt(self, y, t_cur, dt):
         """One step from y with f0 in bufs['K0']: fresh stage-input buffers (kept when
         the step is accepted); returns (stage inputs [ns], y1, err2 device scalar)."""
@@ -91,35 +87,24 @@ class AdaptiveBackprop(object):
         b['Y1'] = y1
         ops.stage_apply(ops.Stage(outs=[(X[0], y, 1.0, 0.0, [(b['K0'], dt * P.beta[0][0])])]), None, None, y)
         for i in range(ns):
-            L = P.launches[i]
             ti = t_cur + dt if P.alpha[i] == 1. else t_cur + P.alpha[i] * dt
-            outs = []
-            for key, dst in (('next', 'X%d' % (i + 1)), ('y1', 'Y1'), ('epart', 'E')):
-                if L[key] is not None:
-                    bt, cb, cf, ks = self._combo(L[key], b, X[i], dt)
-                    outs.append((b[dst], bt, cb, cf, ks))
-            err = None
-            if L['err'] is not None:
-                bt, cb, cf, ks = self._combo(L['err'], b, X[i], dt)
-                err = (self.rows, (bt, cb, cf, ks), y, 0 if L['y1'] is not None else -1, self.atol, self.rtol)
+            # (the host's dt in the coefficients; every k_{i+1} is stored: the dense output's adjoint)
+            outs, err, err_y1, _ = P.launch(i, True, lambda s: X[i] if s == 'X' else b[s], mult=dt)
+            if err is not None:
+                err = (self.rows, err, y, err_y1, self.atol, self.rtol)
             self._rhs(ti, X[i], ops.Stage(f_out=b['K%d' % (i + 1)], outs=outs, err=err))
         return X, y1, ops.sum_f64(self.rows)
 
     def _interp_into(self, out, step, t):
-        """The dense output of an accepted step (integrator._RKAdaptiveFused._interp_into's
-        one-pass form) from the step's y0, y1 and the k's still in bufs; returns the
-        coefficients (on y0, y1, k_0..k_ns) its adjoint needs."""
+        """The dense output of an accepted step from the step's y0, y1 and the k's still in
+        bufs, as one pass; returns the coefficients (on y0, y1, k_0..k_ns) its adjoint needs.
+        The pass keeps every k_j as an operand in stage order (the adjoint's coefficient per
+        k_j), not solver_common.dense_combo's merged form with f1 as the f input."""
         P, b = self.plan, self.bufs
         t0, dt, y0, y1 = step['t0'], step['dt'], step['y0'], step['y1']
         ns = P.ns
-        x = (t - t0) / dt
-        x2, x3, x4 = x * x, x * x * x, x * x * x * x
-        cy0 = 1.0 - 11.0 * x2 + 18.0 * x3 - 8.0 * x4
-        cy1 = -5.0 * x2 + 14.0 * x3 - 8.0 * x4
-        cym = 16.0 * x2 - 32.0 * x3 + 16.0 * x4
-        cf0 = dt * (x - 4.0 * x2 + 5.0 * x3 - 2.0 * x4)
-        cf1 = dt * (x2 - 3.0 * x3 + 2.0 * x4)
-        ck = [cym * dt * P.c_mid[j] for j in range(ns + 1)]
+        cy0, cy1, cym, cf0, cf1 = dense_weights((t - t0) / dt, dt)
+        ck =[cym * dt * P.c_mid[j] for j in range(ns + 1)]
         ck[0] += cf0
         ck[ns] += cf1
         terms = [(b['K%d' % j], ck[j]) for j in range(ns + 1) if ck[j] != 0.0]
@@ -153,47 +138,39 @@ class AdaptiveBackprop(object):
         self.steps = []           # accepted steps: t0, dt, y0, stage inputs, y1
         self.outputs = []         # (output index, 'exact', boundary index) | (output index, 'dense', step, coefs)
         y, t_cur = y0, th[0]
-        kn = 'K%d' % ns
         for i_out in range(1, len(th)):
             next_t = th[i_out]
             while next_t > t_cur:
-                if not (t_cur + dt > t_cur):
-                    raise AssertionError('underflow in dt {}'.format(dt))
-                if self.n_steps >= self.max_num_steps:
-                    raise AssertionError('max_num_steps exceeded ({}>={})'.format(self.n_steps, self.max_num_steps))
+                check_step(t_cur, dt, self.n_steps, self.max_num_steps)
                 X, y1, e2 = self._attempt(y, t_cur, dt)
                 ratio = math.sqrt(float(e2) / y0.numel())  # the one host read of the step
                 if ratio <= 1:
                     self.steps.append({'t0': t_cur, 'dt': dt, 'y0': y, 'yin': X, 'y1': y1})
                     t_cur = t_cur + dt
                     y = y1
-                    b['K0'], b[kn] = b[kn], b['K0']  # the next f0: this step's last stage (FSAL or not)
-                if ratio == 0:
-                    dt = dt * self.ifactor
-                else:
-                    df = 1.0 if ratio < 1 else self.dfactor
-                    dt = dt * min(self.ifactor, max(self.safety / ratio ** (1.0 / self.order), df))
+                    rotate(b, P)  # the next f0: this step's last stage (FSAL or not); _attempt rebinds Y / Y1
+                dt = next_dt(dt, ratio, self.order, self.safety, self.ifactor, self.dfactor)
                 self.n_steps += 1
             if next_t == t_cur or not self.steps:
                 sol[i_out].copy_(y)
                 self.outputs.append((i_out, 'exact', len(self.steps)))
             else:
                 # the k's of the last accepted step are in bufs (K0 / K_ns swapped back for the formula)
-                b['K0'], b[kn] = b[kn], b['K0']
+                rotate(b, P)
                 coefs = self._interp_into(sol[i_out], self.steps[-1], next_t)
-                b['K0'], b[kn] = b[kn], b['K0']
+                rotate(b, P)
                 self.outputs.append((i_out, 'dense', len(self.steps) - 1, coefs))
+        self.func = None  # the backward reads the caller's snapshot, never the module
         return sol
 
     # ------------------------------------------------------------------ backward
-    def backward(self, grad_sol):
-        """The discrete adjoint of the accepted steps and the dense outputs."""
-        P, func = self.plan, self.func
+    def backward(self, grad_sol, o, w):
+        """The discrete adjoint of the accepted steps and the dense outputs.  ``o``: the
+        LaplacianOperands taken in forward (snapshot mode); ``w``: the weights as autograd
+        saved them."""
+        P = self.plan
         ns, S = P.ns, len(self.steps)
-        g = func.graph_for(self.y0)
-        w, tag = func._weights_tensor()
-        w_csc = func.csr_weights(g, w, tag, transpose=True)
-        alpha = func.alpha_train.detach()
+        g, w_csc, alpha = o.g, o.w_csc, o.alpha
         R = self.y0.numel() // self.y0.shape[-1]
         drow = torch.zeros(R, dtype=torch.float64, device=self.y0.device)
         grad_sol = grad_sol.contiguous()
@@ -279,12 +256,11 @@ class AdaptiveBackprop(object):
             pairs_y.append(y_init)
             ybar = out
         ybar = ybar + grad_sol[0]  # sol[0] = y0
-        sig = torch.sigmoid(alpha.double())
-        ga = ops.sum_f64(drow) * (1.0 - sig)
+        ga = alpha_grad(drow, alpha.double())
         gb = None
         if self.add_source and pairs_k:
             ksum = torch.stack(pairs_k, 0).sum(0)
-            gb = ops.dot(ksum, func.stable_x0(self.y0))
+            gb = ops.dot(ksum, o.x0)
         gw = None
         if w.requires_grad and pairs_k:
             C = self.y0.shape[-1]

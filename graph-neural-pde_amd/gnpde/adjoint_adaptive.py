@@ -25,7 +25,7 @@ stay 0).  integrator._OdeintAdjoint runs that as torchdiffeq does — a packed
 This module runs the same loop (integrator._RKAdaptive: the tableau, the initial
 step selection, the controller, the dense output) with the y and a halves kept in
 one packed device state [2, B, N, C] and every stage combination in the K1
-epilogues (integrator._AdaptivePlan: launch i of a step evaluates both halves at
+epilogues (solver_common._AdaptivePlan: launch i of a step evaluates both halves at
 stage input X_i and writes X_{i+1} and the error rows of its half; the CSC launch
 adds the alpha integrand's rows <L^T a_i, y_i>).  The scalar components (alpha,
 beta) are integrated on the host in fp64 from the per-stage sums: one segment-sum
@@ -40,6 +40,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .solver_common import (_AdaptiveState, _adaptive_plan, _node_layout, _to_internal, _to_user, check_step,
+                            dense_combo, dense_weights, laplacian_operands, next_dt, rotate)
 from .utils import MaxNFEException
 
 
@@ -49,14 +51,13 @@ def _f32(v):
 
 class AdaptiveAdjoint(object):
     """The backward of odeint_adjoint for a LaplacianODEFunc with an adaptive
-    adjoint method: ``run(t_h, ans, grad_y)`` -> (grad of y0, {id(param): grad})."""
+    adjoint method: ``run(t_h, ans, grad_y)`` -> (grad of y0, alpha's gradient, beta's
+    or None without add_source), the scalars as host floats."""
 
     def __init__(self, func, params, method, rtol, atol, options=None):
-        from . import integrator as gi
-        self.gi = gi
         self.func, self.params = func, tuple(params)
         self.method = method
-        self.plan = gi._adaptive_plan(method)
+        self.plan = _adaptive_plan(method)
         self.order = float(self.plan.order)
         self.rtol, self.atol = float(rtol), float(atol)
         opts = dict(options or {})
@@ -68,10 +69,10 @@ class AdaptiveAdjoint(object):
 
     # ------------------------------------------------------------------ setup
     def _setup(self, y_like):
-        gi, P, func = self.gi, self.plan, self.func
+        P, func = self.plan, self.func
         C = y_like.shape[-1]
         packed = torch.empty((2,) + tuple(y_like.shape), dtype=torch.float32, device=y_like.device)
-        st = gi._AdaptiveState(P, packed, False)
+        st = _AdaptiveState(P, packed, False)
         self.bufs = st.bufs
         self.scale = st.scale
         R = y_like.numel() // C
@@ -84,17 +85,13 @@ class AdaptiveAdjoint(object):
         self.nrec = 3 + ns + (ns + 1) + 4
         self.rec = torch.zeros(self.nrec, dtype=torch.float64, device=y_like.device)
         self.rec_host = torch.empty(self.nrec, dtype=torch.float64, pin_memory=True)
-        g = func.graph_for(y_like)
-        w, tag = func._weights_tensor()
-        self.g = g
-        self.w_csr = func.csr_weights(g, w, tag)
-        self.w_csc = func.csr_weights(g, w, tag, transpose=True)
-        self.x0 = func.stable_x0(y_like) if self.add_source else None
-        alpha = func.alpha_train.detach()
+        o = laplacian_operands(func, y_like, csr=True)
+        self.g, self.w_csr, self.w_csc, self.x0 = o.g, o.w_csr, o.w_csc, o.x0
+        alpha = o.alpha
         self.alpha = alpha.float().reshape(()).contiguous()
         # y-half: -f(y) = (-sigma(alpha))(A y - y) + (-beta) x0 from the same K1 (alpha taken as given)
         self.neg_sig = (-torch.sigmoid(alpha.float())).reshape(()).contiguous()
-        self.neg_beta = (-func.beta_train.detach().float()).reshape(()).contiguous()
+        self.neg_beta = (-o.beta.float()).reshape(()).contiguous()
         self.one_minus_sig = 1.0 - 1.0 / (1.0 + math.exp(-float(alpha)))
 
     def _read(self):
@@ -125,32 +122,16 @@ class AdaptiveAdjoint(object):
     def _beta_slot(self, j):
         return 3 + self.plan.ns + j
 
-    def _combo(self, spec, h, x):
-        b = self.bufs
-        base, terms, cfc = spec
-        bt = {'Y': b['Y'], 'X': x, 'E': b.get('E'), None: None}[base]
-        bt = bt[h] if bt is not None else None
-        return bt, (1.0 if bt is not None else 0.0), cfc, [(b[k][h], c) for k, c in terms]
-
     def _launch(self, i, mid):
         P, b = self.plan, self.bufs
-        L = P.launches[i]
         x = b['X%d' % i]
         j = i + 1
         stages = []
-        for h in (0, 1):
-            outs = []
-            for key, dst in (('next', 'X%d' % (i + 1)), ('y1', 'Y1'), ('epart', 'E')):
-                if L[key] is not None:
-                    bt, cb, cf, ks = self._combo(L[key], h, x)
-                    outs.append((b[dst][h], bt, cb, cf, ks))
-            err = None
-            if L['err'] is not None:
-                bt, cb, cf, ks = self._combo(L['err'], h, x)
-                err = (self.rows[h], (bt, cb, cf, ks), b['Y'][h], 0 if L['y1'] is not None else -1, self.atol,
-                       self.rtol)
-            f_out = b['K%d' % j][h] if (j in P.store or (mid and j in P.store_mid)) else None
-            stages.append(ops.Stage(f_out=f_out, outs=outs, err=err, scale=self.scale))
+        for h in (0, 1):  # the plan's symbols resolved to half h of the packed buffers
+            outs, err, err_y1, store = P.launch(i, mid, lambda s: (x if s == 'X' else b[s])[h])
+            if err is not None:
+                err = (self.rows[h], err, b['Y'][h], err_y1, self.atol, self.rtol)
+            stages.append(ops.Stage(f_out=b['K%d' % j][h] if store else None, outs=outs, err=err, scale=self.scale))
         self._rhs(x, stages[0], stages[1], 2 + j, self._beta_slot(j))
 
     def _step(self, mid):
@@ -230,10 +211,7 @@ class AdaptiveAdjoint(object):
         t_cur = t0
         last = None
         while t1 > t_cur:
-            if not (t_cur + dt > t_cur):
-                raise AssertionError('underflow in dt {}'.format(dt))
-            if self.n_steps >= self.max_num_steps:
-                raise AssertionError('max_num_steps exceeded ({}>={})'.format(self.n_steps, self.max_num_steps))
+            check_step(t_cur, dt, self.n_steps, self.max_num_steps)
             mid = t_cur + dt >= t1
             self.scale.fill_(dt)
             self._step(mid)
@@ -250,58 +228,26 @@ class AdaptiveAdjoint(object):
                 t_cur = t_cur + dt
                 s0 = s1
                 k0 = [v[ns] for v in kk]
-                self._rotate()
-            if ratio == 0:
-                dt = dt * self.ifactor
-            else:
-                df = 1.0 if ratio < 1 else self.dfactor
-                dt = dt * min(self.ifactor, max(self.safety / ratio ** (1.0 / self.order), df))
+                rotate(b, P)
+            dt = next_dt(dt, ratio, self.order, self.safety, self.ifactor, self.dfactor)
             self.n_steps += 1
         if last is None or t1 == t_cur:
             return self.bufs['Y'][1], s0
         return self._interp(last, t1, t_cur)
-
-    def _rotate(self):
-        b, kn = self.bufs, 'K%d' % self.plan.ns
-        b['Y'], b['Y1'] = b['Y1'], b['Y']
-        b['K0'], b[kn] = b[kn], b['K0']
-        if self.plan.fsal:
-            b['X%d' % (self.plan.ns - 1)] = b['Y1']
 
     def _interp(self, last, t, t1):
         """torchdiffeq's 4th-order dense output of the last accepted step (integrator.
         _RKAdaptive._interp) for the a-half (one stage pass) and the scalars."""
         P = self.plan
         t0, dt, d, s0, s1, kk = last
-        x = (t - t0) / (t1 - t0)
-        x2, x3, x4 = x * x, x * x * x, x * x * x * x
-        cy0 = 1.0 - 11.0 * x2 + 18.0 * x3 - 8.0 * x4
-        cy1 = -5.0 * x2 + 14.0 * x3 - 8.0 * x4
-        cym = 16.0 * x2 - 32.0 * x3 + 16.0 * x4
-        cf0 = dt * (x - 4.0 * x2 + 5.0 * x3 - 2.0 * x4)
-        cf1 = dt * (x2 - 3.0 * x3 + 2.0 * x4)
+        wts = cy0, cy1, cym, cf0, cf1 = dense_weights((t - t0) / (t1 - t0), dt)
         ns = P.ns
         h = 1
         y0, y1, f0, f1 = d['Y'][h], d['Y1'][h], d['K0'][h], d['K%d' % ns][h]
-        coef = {}
-        order = []
-
-        def add(tn, c):
-            if c == 0.0:
-                return
-            if id(tn) not in coef:
-                coef[id(tn)] = [tn, 0.0]
-                order.append(id(tn))
-            coef[id(tn)][1] += c
-        add(y1, cy1)
-        for j in range(ns + 1):
-            if P.c_mid[j] != 0.0:
-                add(d['K%d' % j][h] if j < ns else f1, cym * dt * P.c_mid[j])
-        add(f0, cf0)
-        cf_f1 = coef.pop(id(f1))[1] + cf1 if id(f1) in coef else cf1
-        terms = [tuple(coef[k]) for k in order if k in coef]
+        # (every [h] is a fresh view: K0's c_mid term and f0's stay two entries, which the Stage merges by address)
+        cb, cf_f1, terms = dense_combo(P, wts, dt, y1, f0, f1, lambda j: d['K%d' % j][h])
         out = torch.empty_like(y0)
-        ops.stage_apply(ops.Stage(outs=[(out, y0, cy0 + cym, cf_f1, terms)]), f1, y0, y0)
+        ops.stage_apply(ops.Stage(outs=[(out, y0, cb, cf_f1, terms)]), f1, y0, y0)
         sv = []
         for c in range(len(s0)):
             k = kk[c]
@@ -311,34 +257,23 @@ class AdaptiveAdjoint(object):
 
     # ------------------------------------------------------------------ the backward
     def run(self, t_h, ans, grad_y):
-        gi, func = self.gi, self.func
-        lay = gi._node_layout(func, ans[0])
+        func = self.func
+        lay = _node_layout(func, ans[0])
         if lay is not None:
             func._layout = lay
         try:
             self._setup(ans[0])
             b = self.bufs
-
-            def load(dst, src):
-                if lay is None:
-                    dst.copy_(src)
-                elif (self.C * 4) % 16 == 0:
-                    ops.rows_copy(src.contiguous(), dst, order=lay.order)
-                else:
-                    torch.index_select(src.reshape(-1, self.C), 0, lay.order, out=dst.view(-1, self.C))
-            load(b['Y'][1], grad_y[-1])
+            _to_internal(grad_y[-1], lay, out=b['Y'][1])
             s = [0.0] + ([0.0] if self.add_source else [])
             for i in range(len(t_h) - 1, 0, -1):
-                load(b['Y'][0], ans[i])
+                _to_internal(ans[i], lay, out=b['Y'][0])
                 if i < len(t_h) - 1:
-                    load(b['Y'][1], a_user)
+                    _to_internal(a_user, lay, out=b['Y'][1])
                 a_end, s = self._interval(-t_h[i], -t_h[i - 1], s)
                 a_user = torch.empty_like(grad_y[i - 1])
-                gi._to_user(a_end, a_user, lay)
+                _to_user(a_end, a_user, lay)
                 a_user += grad_y[i - 1]
         finally:
             func._layout = None
-        grads = {id(func.alpha_train): s[0]}
-        if self.add_source:
-            grads[id(func.beta_train)] = s[1]
-        return a_user, grads
+        return a_user, s[0], (s[1] if self.add_source else None)

@@ -31,62 +31,13 @@ import torch
 
 from . import _lib, ops
 from ._cache import _tensor_key
+from .adaptive_backprop import AdaptiveBackprop
+from .adjoint_adaptive import AdaptiveAdjoint
+from .solver_common import (_TABLEAUS, _AdaptivePlan, _AdaptiveState, _KrylovPlan, _adaptive_plan,  # noqa: F401
+                            _entry_copy, _krylov_plan, _node_layout, _to_internal, _to_user, alpha_grad, check_step,
+                            dense_combo, dense_weights, laplacian_adjoint_ok, laplacian_operands, next_dt,
+                            param_grads, rotate)
 from .utils import MaxNFEException
-
-# Dormand-Prince-Shampine (torchdiffeq dopri5.py)
-_DP_ALPHA = [1 / 5, 3 / 10, 4 / 5, 8 / 9, 1., 1.]
-_DP_BETA = [
-    [1 / 5],
-    [3 / 40, 9 / 40],
-    [44 / 45, -56 / 15, 32 / 9],
-    [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
-    [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656],
-    [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84],
-]
-_DP_C_SOL = [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84, 0]
-_DP_C_ERROR = [
-    35 / 384 - 1951 / 21600,
-    0,
-    500 / 1113 - 22642 / 50085,
-    125 / 192 - 451 / 720,
-    -2187 / 6784 - -12231 / 42400,
-    11 / 84 - 649 / 6300,
-    -1. / 60.,
-]
-_DP_C_MID = [
-    6025192743 / 30085553152 / 2, 0, 51252292925 / 65400821598 / 2, -2691868925 / 45128329728 / 2,
-    187940372067 / 1594534317056 / 2, -1776094331 / 19743644256 / 2, 11237099 / 235043384 / 2,
-]
-
-# Bogacki-Shampine 3(2) (torchdiffeq bosh3.py)
-_BS_ALPHA = [1 / 2, 3 / 4, 1.]
-_BS_BETA = [[1 / 2], [0., 3 / 4], [2 / 9, 1 / 3, 4 / 9]]
-_BS_C_SOL = [2 / 9, 1 / 3, 4 / 9, 0.]
-_BS_C_ERROR = [2 / 9 - 7 / 24, 1 / 3 - 1 / 4, 4 / 9 - 1 / 3, -1 / 8]
-_BS_C_MID = [0., 0.5, 0., 0.]
-
-# Heun-Euler 2(1) (torchdiffeq adaptive_heun.py; the reference's default adjoint_method,
-# src/run_GNN.py:334, src/best_params.py)
-_AH_ALPHA = [1.]
-_AH_BETA = [[1.]]
-_AH_C_SOL = [0.5, 0.5]
-_AH_C_ERROR = [0.5, -0.5]
-_AH_C_MID = [0.5, 0.]
-
-# Runge-Kutta-Fehlberg 2(1) (torchdiffeq fehlberg2.py)
-_FE_ALPHA = [1 / 2, 1.]
-_FE_BETA = [[1 / 2], [1 / 256, 255 / 256]]
-_FE_C_SOL = [1 / 512, 255 / 256, 1 / 512]
-_FE_C_ERROR = [-1 / 512, 0., 1 / 512]
-_FE_C_MID = [0., 0.5, 0.]
-
-# name -> (order, alpha, beta, c_sol, c_error, c_mid)
-_TABLEAUS = {
-    'dopri5': (5, _DP_ALPHA, _DP_BETA, _DP_C_SOL, _DP_C_ERROR, _DP_C_MID),
-    'bosh3': (3, _BS_ALPHA, _BS_BETA, _BS_C_SOL, _BS_C_ERROR, _BS_C_MID),
-    'fehlberg2': (2, _FE_ALPHA, _FE_BETA, _FE_C_SOL, _FE_C_ERROR, _FE_C_MID),
-    'adaptive_heun': (2, _AH_ALPHA, _AH_BETA, _AH_C_SOL, _AH_C_ERROR, _AH_C_MID),
-}
 
 FIXED_METHODS = ('euler', 'midpoint', 'rk4')
 ADAPTIVE_METHODS = ('dopri5', 'bosh3', 'fehlberg2', 'adaptive_heun')
@@ -530,9 +481,7 @@ class _LaplacianFixedGridFn(torch.autograd.Function):
         else:
             sol[0].copy_(y0d)
             y = y0d
-        sig = not func.opt.get('no_alpha_sigmoid', False)
         try:
-            gr = func.graph_for(y0)
             starts, stage_inputs = [], []
             j = 1
             for n_step, (ta, tb) in enumerate(steps):
@@ -560,17 +509,10 @@ class _LaplacianFixedGridFn(torch.autograd.Function):
             # Function's forward, so the module's cached buffer counts as no_grad-made and a
             # later no_grad call with new weights would refresh it in place under this node's
             # pending backward).
-            ctx.alpha = func.alpha_train.detach().clone()
-            ctx.a_dev = torch.sigmoid(ctx.alpha) if sig else ctx.alpha
+            ctx.o = o = laplacian_operands(func, y0, private_csc=True, snapshot=True)
+            ctx.a_dev = torch.sigmoid(o.alpha) if o.sig else o.alpha
             ctx.a_scale = ctx.a_dev.reshape(()).float().contiguous()
             ctx.a_host = _host_scalar(ctx.a_dev) if method != 'rk4' else None
-            w, tag = func._weights_tensor()
-            src = w.detach().float() if w.dtype != torch.float32 else w.detach()
-            ctx.w_csc = gr.gather_weights(src, transpose=True)
-            ctx.gr = gr
-            ctx.sig = sig
-            ctx.add_source = bool(func.opt.get('add_source', False))
-            ctx.x0 = func.stable_x0(y0).clone() if ctx.add_source else None
         finally:
             func._layout = None
         ctx.func, ctx.method, ctx.steps, ctx.t_h, ctx.lay = func, method, steps, t_h, lay
@@ -583,14 +525,11 @@ class _LaplacianFixedGridFn(torch.autograd.Function):
         g_sol = g_sol.contiguous()
         lay = ctx.lay
         with torch.no_grad():
-            gr, w_csc = ctx.gr, ctx.w_csc
+            gr, w_csc, sig, add_source, x0 = ctx.o.g, ctx.o.w_csc, ctx.o.sig, ctx.o.add_source, ctx.o.x0
             one = _device_one(g_sol.device)
-            sig = ctx.sig
             a_dev = ctx.a_dev
             a = ctx.a_host() if ctx.a_host is not None else None  # euler / midpoint combinations
             asc = ctx.a_scale  # rk4: coef_scale of every adjoint launch (cb unscaled, cf and c_j times a)
-            add_source = ctx.add_source
-            x0 = ctx.x0
 
             def u_of(v):  # (A^T - I) v
                 return ops.spmm_rhs(gr, w_csc, v, alpha=one, rhs=True, alpha_sigmoid=False, transpose=True)
@@ -736,12 +675,6 @@ def _device_one(device):
     return one
 
 
-def _node_layout(func, y0):
-    """The locality numbering (ops.NodeLayout) the fused path keeps the state in, or None."""
-    fn = getattr(func, 'node_layout', None)
-    return fn(y0) if fn is not None else None
-
-
 # Host copies of time grids.  A solve needs t on the host (the loop is there); a
 # device t costs a device->host copy, i.e. a wait for everything queued before it.
 # The values of a device t are kept per tensor object (and version), so a model
@@ -809,41 +742,6 @@ def odeint_fixed(func, y0, t, method, step_size=None, combine=None, graph=None):
         solution.append(yc)
         j += 1
     return torch.stack(solution, 0)
-
-
-def _entry_copy(y0, buf, sol0, order):
-    """buf = y0 in the solve's numbering (order: internal row k holds user row
-    order[k]), sol0 = y0: one pass (gnpde_rows_copy) when rows are 16-byte
-    multiples, torch copies otherwise."""
-    if y0.is_cuda and (y0.shape[-1] * y0.element_size()) % 16 == 0 and y0.is_contiguous():
-        ops.rows_copy(y0, buf, order=order, dst_copy=sol0)
-        return
-    sol0.copy_(y0)
-    if order is None:
-        buf.copy_(y0)
-    else:
-        C = y0.shape[-1]
-        torch.index_select(y0.reshape(-1, C), 0, order, out=buf.view(-1, C))
-
-
-def _to_internal(src, lay):
-    """src (caller's numbering) gathered into the solve's numbering: a fresh tensor."""
-    if src.is_cuda and (src.shape[-1] * src.element_size()) % 16 == 0 and src.is_contiguous():
-        dst = torch.empty_like(src)
-        ops.rows_copy(src, dst, order=lay.order)
-        return dst
-    return lay.to_internal(src)
-
-
-def _to_user(src, dst, lay):
-    """dst = src in the caller's numbering (a fresh solution slice)."""
-    if lay is None:
-        dst.copy_(src)
-    elif src.is_cuda and (src.shape[-1] * src.element_size()) % 16 == 0:
-        ops.rows_copy(src, dst, order=lay.new_id)
-    else:
-        C = src.shape[-1]
-        torch.index_select(src.reshape(-1, C), 0, lay.new_id, out=dst.view(-1, C))
 
 
 def _solve_fused(func, y0, t_h, steps, method, graph):
@@ -1070,10 +968,7 @@ class _RKAdaptive(object):
         for i in range(1, len(t)):
             next_t = t[i]
             while next_t > t_cur:
-                if not bool(t_cur + dt > t_cur):
-                    raise AssertionError('underflow in dt {}'.format(float(dt)))
-                if self.n_steps >= self.max_num_steps:
-                    raise AssertionError('max_num_steps exceeded ({}>={})'.format(self.n_steps, self.max_num_steps))
+                check_step(t_cur, dt, self.n_steps, self.max_num_steps)
                 y1, f1, y1_err, k = self._step(y, f, t_cur, dt)
                 error_tol = self.atol + self.rtol * torch.max(y.abs(), y1.abs())
                 error_ratio = self.norm(y1_err / error_tol).abs()
@@ -1091,184 +986,7 @@ class _RKAdaptive(object):
         return torch.stack(solution, 0)
 
 
-# --------------------------------------------------------------------------- fused adaptive steps
-# An embedded Runge-Kutta step of torchdiffeq's adaptive solver (dopri5 — the method
-# of every src/best_params.py entry — bosh3, fehlberg2, adaptive_heun) with every
-# stage combination and the error estimate in the RHS epilogues (gnpde_stage_
-# epilogue_t, the wide epilogue): launch i evaluates k_{i+1} = f(X_i) and writes the
-# next stage input X_{i+1} from the rows it holds; the last launch forms the rows of
-# the squared error norm.  One host read per step (the norm); no separate
-# combination passes besides the step's first stage input.  The plan below derives
-# every launch's operands from the tableau, choosing per combination the form that
-# reads fewest state arrays:
-#   from the launch's own input:  X_{i+1} = X_i + dt sum_j (b_{i+1,j} - b_{i,j}) k_j + dt b_{i+1,i+1} f
-#   from the step start:          X_{i+1} = y0  + dt sum_j b_{i+1,j} k_j + dt b_{i+1,i+1} f
-# (same values up to rounding: a combination of the k's scaled by dt, never a
-# difference of states, so the error estimate keeps its precision).
-
-def _nz(c):
-    return c != 0.0
-
-
-class _AdaptivePlan(object):
-    """Per-launch operands of one step of an embedded tableau.
-
-    Symbols: 'Y' the step start y0, 'X' the launch's own input, 'E' the error
-    partial, 'K<j>' stage derivative j (K0 = f0 from the previous step).  Each
-    combination is (base symbol or None, [(K<j>, coefficient / dt)...], f
-    coefficient / dt); dt multiplies every k and f coefficient at run time."""
-
-    def __init__(self, method):
-        order, alpha, beta, c_sol, c_err, c_mid = _TABLEAUS[method]
-        self.method, self.order, self.alpha, self.beta = method, order, alpha, beta
-        self.c_sol, self.c_err, self.c_mid = c_sol, c_err, c_mid
-        ns = len(alpha)
-        self.ns = ns
-        self.fsal = c_sol[-1] == 0 and list(c_sol[:-1]) == list(beta[-1])
-        self.launches = []
-        reads = []  # K indices each launch reads
-        for i in range(ns):
-            L = {'next': None, 'y1': None, 'epart': None, 'err': None}
-            rd = set()
-            if i < ns - 1:
-                d = [(j, beta[i + 1][j] - beta[i][j]) for j in range(i + 1)]
-                d = [(j, c) for j, c in d if _nz(c)]
-                yv = [(j, beta[i + 1][j]) for j in range(i + 1) if _nz(beta[i + 1][j])]
-                if len(d) <= len(yv) + 1:
-                    L['next'] = ('X', [('K%d' % j, c) for j, c in d], beta[i + 1][i + 1])
-                    rd |= {j for j, _ in d}
-                else:
-                    L['next'] = ('Y', [('K%d' % j, c) for j, c in yv], beta[i + 1][i + 1])
-                    rd |= {j for j, _ in yv}
-            else:
-                if not self.fsal:
-                    yv = [(j, c_sol[j]) for j in range(ns) if _nz(c_sol[j])]
-                    L['y1'] = ('Y', [('K%d' % j, c) for j, c in yv], c_sol[ns])
-                    rd |= {j for j, _ in yv}
-            reads.append(rd)
-            self.launches.append(L)
-        # the error combination e = dt sum_j c_err[j] k_j (k_ns = the last launch's f): all in
-        # the last launch, or its first ns terms precomputed by the launch before (a second
-        # output 'E') when that launch already reads most of their operands
-        last = ns - 1
-        ev = [(j, c_err[j]) for j in range(ns) if _nz(c_err[j])]
-        direct = {j for j, _ in ev if j < ns} - reads[last]
-        pre_ok = ns >= 2
-        if pre_ok:
-            held = reads[last - 1] | {last}  # launch ns-2 reads its operands and holds k_{ns-1} = its own f
-            pre_cost = 2 + len({j for j, _ in ev} - held)
-            pre_ok = pre_cost < len(direct) + (0 if last in reads[last] else 0)
-        if pre_ok:
-            self.launches[last - 1]['epart'] = (None, [('K%d' % j, c) for j, c in ev if j < last], c_err[last])
-            self.launches[last]['err'] = ('E', [], c_err[ns])
-            reads[last - 1] |= {j for j, _ in ev if j < last}
-        else:
-            self.launches[last]['err'] = (None, [('K%d' % j, c) for j, c in ev], c_err[ns])
-            reads[last] |= {j for j, _ in ev}
-        self.reads = reads
-        # k_j stored when a later launch reads it (k_ns: always, the next step's f0)
-        self.store = set()
-        for i in range(ns):
-            for j in reads[i]:
-                if j >= 1:
-                    self.store.add(j)
-        self.store.add(ns)
-        # dense output (a step that may cross an output time): every k with a c_mid term
-        self.store_mid = {j for j in range(1, ns + 1) if _nz(c_mid[j])} - self.store
-
-    def state_passes(self):
-        """Full-state reads / writes per step beyond each launch's own gathers,
-        input row and one output (the bench's overhead check)."""
-        r = 2  # the step's first stage input: y0 and k0
-        w = 1
-        for i, L in enumerate(self.launches):
-            outs = [c for c in (L['next'], L['y1'], L['epart']) if c is not None]
-            r += len(self.reads[i]) + sum(1 for c in outs if c[0] in ('Y', 'E'))
-            if L['err'] is not None:
-                r += 1 + (1 if L['err'][0] == 'E' else 0)  # y0 for the tolerance, E
-            stored = (i + 1) in self.store
-            w += len(outs) + (1 if stored else 0) - 1
-        return r, w
-
-
-_PLANS = {}
-
-
-def _adaptive_plan(method):
-    p = _PLANS.get(method)
-    if p is None:
-        p = _PLANS[method] = _AdaptivePlan(method)
-    return p
-
-
-class _KrylovPlan(object):
-    """The step of an FSAL tableau for an affine RHS f(y) = L y + s in the Krylov basis
-    u_p = (dt L)^p f0 (u_0 = f0 = f(y0)).  Every stage derivative is a fixed
-    combination of them: k_0 = u_0, k_{i+1} = f(y0 + dt sum_j beta[i][j] k_j)
-    = k_0 + sum_j beta[i][j] (dt L) k_j, so k_i = sum_p B[i][p] u_p with
-    B[i+1][p] = sum_j beta[i][j] B[j][p-1].  A step is ns launches of the linear part,
-    u_{p+1} = dt L u_p, each reading only its own input (no stage operand); the last
-    (over u_{ns-1}, with f_lin = 1: f' = u_{ns-1} + u_ns) forms
-      y1  = y0 + dt sum_p G[p] u_p,                 G[p]   = sum_j c_sol[j] B[j][p]
-      f1  = sum_p B[ns][p] u_p                      (the next step's f0: unscaled)
-      e   = dt sum_p Eps[p] u_p,                    Eps[p] = sum_j c_err[j] B[j][p]
-    with u_ns = f' - u_{ns-1} substituted.  Mathematically the tableau's step; Eps[p]
-    vanishes exactly for p below the embedded order (the order conditions of the
-    linear problem), which the fp64 sums leave at rounding level and the plan zeroes,
-    so the error estimate carries no stage-combination cancellation noise.  Dense
-    output: y_mid = y0 + dt (sum_p Mu[p] u_p + c_mid[ns] f1), Mu[p] = sum_{j<ns}
-    c_mid[j] B[j][p], with y1 restated on the u_p (one pass over ns + 2 rows)."""
-
-    def __init__(self, plan):
-        ns, beta = plan.ns, plan.beta
-        B = [[1.0]]
-        for i in range(ns):
-            B.append([1.0] + [sum(beta[i][j] * B[j][p - 1] for j in range(p - 1, i + 1))
-                              for p in range(1, i + 2)])
-        self.B = B
-
-        def comb(c, upto):
-            v = [sum(c[j] * B[j][p] for j in range(p, upto)) for p in range(ns + 1)]
-            big = max(1.0, max(abs(x) for x in v))
-            return [0.0 if abs(x) < 1e-12 * big else x for x in v]
-        self.G = comb(plan.c_sol, ns + 1)
-        self.Eps = comb(plan.c_err, ns + 1)
-        self.Mu = comb(plan.c_mid, ns)
-        self.Bn = list(B[ns])
-        self.ns = ns
-
-    def last_launch_terms(self):
-        """(y1 terms, (f1 terms, f1 cf), (error terms, error cf)) of the last launch over
-        u_{ns-1}, as [(p, coefficient)] with u_ns = f' - u_{ns-1} substituted."""
-        ns = self.ns
-
-        def sub(v):
-            t = [(p, v[p]) for p in range(ns - 1) if v[p] != 0.0]
-            c = v[ns - 1] - v[ns]
-            if c != 0.0:
-                t.append((ns - 1, c))
-            return t, v[ns]
-        y1 = [(p, self.G[p]) for p in range(ns) if self.G[p] != 0.0]
-        return y1, sub(self.Bn), sub(self.Eps)
-
-    def state_passes(self):
-        """Full-state reads / writes per step beyond each launch's gathers, input row
-        and one output: the last launch reads y0 (the y1 base and the tolerance) and
-        u_0 .. u_{ns-2}, and writes a second output (f1)."""
-        return self.ns, 1
-
-
 KRYLOV_STEP = os.environ.get('GNPDE_KRYLOV_STEP', '1') != '0'
-_KRYLOV_PLANS = {}
-
-
-def _krylov_plan(plan):
-    """The _KrylovPlan of a tableau plan, built once (its fp64 sums cost ~50 us of host
-    time, which every solve paid before its first launch)."""
-    k = _KRYLOV_PLANS.get(plan.method)
-    if k is None:
-        k = _KRYLOV_PLANS[plan.method] = _KrylovPlan(plan)
-    return k
 # The dense output of a one-output-time Krylov solve folded into its steps' last launch
 # (ABI 8 Stage.dense; GNPDE_DENSE_FOLD=0: the separate pass of _interp_into)
 DENSE_FOLD = os.environ.get('GNPDE_DENSE_FOLD', '1') != '0'
@@ -1332,27 +1050,31 @@ class _LaplacianAdaptiveFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y0, alpha_train, beta_train, w, func, t_h, method, rtol, atol, first_step, max_num_steps):
-        from .adaptive_backprop import AdaptiveBackprop
         with torch.no_grad():
             solver = AdaptiveBackprop(func, y0.detach(), t_h, method, rtol, atol, first_step, max_num_steps)
             sol = solver.forward()
+            # everything the backward reads is taken NOW, after the forward launches are queued (as
+            # _LaplacianFixedGridFn.forward): another forward, a new graph, weights or x0, or a no_grad
+            # solve refreshing the module's cached buffers before this backward must not change its gradient
+            ctx.o = laplacian_operands(func, solver.y0, snapshot=True)
         odeint.last_n_steps = solver.n_steps
         ctx.solver = solver
-        ctx.shapes = (alpha_train.shape, alpha_train.dtype, beta_train.shape, beta_train.dtype)
+        ctx.save_for_backward(w, alpha_train, beta_train)  # an in-place edit before the backward is autograd's error
         return sol
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.solver is None:
+            raise RuntimeError("gnpde: the adaptive backprop node's buffers (every accepted step's stage inputs) "
+                               "were released after its first backward; run the forward again")
+        w, alpha_train, beta_train = ctx.saved_tensors
         with torch.no_grad():
-            ybar, ga, gb, gw = ctx.solver.backward(g)
-        ctx.solver = None
-        ash, adt, bsh, bdt = ctx.shapes
+            ybar, ga, gb, gw = ctx.solver.backward(g, ctx.o, w)
+        ctx.solver = ctx.o = None  # frees every stored stage input
         need = ctx.needs_input_grad
         gy = ybar.view(g.shape[1:]) if need[0] else None
-        gal = ga.to(adt).reshape(ash) if need[1] else None
-        gbe = None
-        if need[2]:
-            gbe = gb.to(bdt).reshape(bsh) if gb is not None else torch.zeros(bsh, dtype=bdt, device=g.device)
+        gal, gbe = (param_grads([p], [(alpha_train, ga), (beta_train, gb)])[0] if n else None
+                    for p, n in zip((alpha_train, beta_train), need[1:3]))
         gwo = gw if need[3] else None
         return (gy, gal, gbe, gwo) + (None,) * 7
 
@@ -1379,60 +1101,6 @@ ADAPTIVE_GRAPH = os.environ.get('GNPDE_ADAPTIVE_GRAPH', '1') != '0'
 AFFINE_STAGE = os.environ.get('GNPDE_AFFINE_STAGE', '1') != '0'
 ADAPTIVE_SPEC = os.environ.get('GNPDE_ADAPTIVE_SPEC', '1') != '0'  # steps enqueued ahead (_integrate)
 _ADAPTIVE_CACHE = weakref.WeakKeyDictionary()  # module -> (key, _AdaptiveState)
-
-
-class _AdaptiveState(object):
-    """Buffers and captured step graphs of one module's fused adaptive solves of one
-    state shape and tolerance (kept across odeint calls, like _StatePool)."""
-
-    def __init__(self, plan, y0, host):
-        new = lambda: torch.empty_like(y0, memory_format=torch.contiguous_format)  # noqa: E731
-        b = {'Y': new(), 'Y1': new(), 'K0': new()}
-        for j in sorted(plan.store | plan.store_mid):
-            b['K%d' % j] = new()
-        xa, xb = new(), new()
-        for i in range(plan.ns):
-            b['X%d' % i] = b['Y1'] if (plan.fsal and i == plan.ns - 1) else (xa if i % 2 == 0 else xb)
-        if any(L['epart'] is not None for L in plan.launches):
-            b['E'] = new()
-        self.bufs = b
-        self.rows = torch.empty(y0.numel() // y0.shape[-1], dtype=torch.float64, device=y0.device)
-        # the step size the stage coefficients are scaled by (device fp32 scalar; the host-stage
-        # test RHS objects apply it in their own precision)
-        self.scale = torch.zeros((), dtype=torch.float32 if not host else torch.float64, device=y0.device)
-        # the device controller's step size (fp64) and its record {ratio, dt, next dt} (device solves)
-        # h = {h0, d1, first step} of the device initial-step selection; dt is h[2] (a view), so
-        # the first step's size and scale are in place when the selection ends
-        self.h = None if host else torch.zeros(3, dtype=torch.float64, device=y0.device)
-        self.dt = None if host else self.h[2]
-        self.rec = None if host else torch.zeros(4, dtype=torch.float64, device=y0.device)
-        self.ws = None if host else torch.empty(_lib.fn("gnpde_dot_workspace_bytes")(), dtype=torch.uint8,
-                                                device=y0.device)
-        self.rec_host, self.rec_slot = None, 0  # pinned copies of rec (_rec_reader)
-        # the folded dense output (DENSE_FOLD): the device time {step start, output time} the controller
-        # advances, the slot holding the output array's address, the output row map (a copy: the
-        # captured launch reads this buffer whatever layout object the solve has)
-        # one device record {t0, t_out, output address} (fp64 / fp64 / int64 views) set per solve by one
-        # copy from a pinned host twin
-        self.dsc = None if host else torch.zeros(3, dtype=torch.float64, device=y0.device)
-        self.dsc_host = None if host else torch.zeros(3, dtype=torch.float64, pin_memory=True)
-        self.dsc_np = None if host else self.dsc_host.numpy()  # (host writes through numpy: no torch ops)
-        self.tdev = None if host else self.dsc[:2]
-        self.dslot = None if host else self.dsc[2:].view(torch.int64)
-        self.dtab = None if host else torch.zeros(_lib.DENSE_SLOTS + 1, dtype=torch.float32, device=y0.device)
-        self.drows, self.drows_src = None, None
-        # the initial-step selection from the f0 / probe launches' row sums (INIT_ROWS): a second
-        # row array (the f0 launch's scale_rows) and the reduction's workspace
-        self.rows2, self.iws = None, None
-        self.side = None  # the second stream of the initial step (LIN_INIT)
-        # the captured prologue of a lin_init solve (f0 and the initial-step launches) and the
-        # workspaces of its two reductions (phase 0 runs beside the probe: two buffers)
-        self.pro = None
-        self.iws0 = self.iws1 = None
-        self.canon = None  # the y / f0 buffer binding every solve starts from (_integrate)
-        self.graphs = {}   # (id Y, id K0, mid, fold, renumbered) -> (graph, error-sum tensor)
-        self.mempool = None
-        self.warm = False
 
 
 class _RKAdaptiveFused(_RKAdaptive):
@@ -1487,37 +1155,22 @@ class _RKAdaptiveFused(_RKAdaptive):
             return pair
         return v
 
-    def _combo(self, spec, bufs, x):
-        """(base tensor, cb, cf, [(k tensor, c)]) of a plan combination; the k and f
-        coefficients are the tableau's, scaled by dt on the device (Stage.scale)."""
-        base, terms, cfc = spec
-        bt = {'Y': bufs['Y'], 'X': x, 'E': bufs.get('E'), None: None}[base]
-        return bt, (1.0 if bt is not None else 0.0), cfc, [(bufs[k], c) for k, c in terms]
-
     def _launch(self, i, st, x, t, mid):
         P = self.plan
         bufs = st.bufs
-        L = P.launches[i]
         lin = self.affine and i == 0
         if lin:
             # the affine first stage: the launch reads k0 and forms k1 = k0 + dt b00 L k0 (Stage.f_lin),
             # never X0 = y0 + dt b00 k0; its combinations on X0 are restated on y0 (X0 = y0 + dt b00 k0)
             x = bufs['K0']
-        outs = []
-        for key, dst in (('next', 'X%d' % (i + 1)), ('y1', 'Y1'), ('epart', 'E')):
-            if L[key] is not None:
-                spec = self._on_y0(L[key]) if lin else L[key]
-                b, cb, cf, ks = self._combo(spec, bufs, x)
-                outs.append((bufs[dst], b, cb, cf, ks))
-        err = None
-        if L['err'] is not None:
-            spec = self._on_y0(L['err']) if lin else L['err']
-            if lin and L['y1'] is None:
+        # (the k and f coefficients are the tableau's, scaled by dt on the device: Stage.scale)
+        outs, err, err_y1, store = P.launch(i, mid, lambda s: x if s == 'X' else bufs[s],
+                                            restate=self._on_y0 if lin else None)
+        if err is not None:
+            if lin and err_y1 < 0:
                 raise RuntimeError("gnpde: an affine one-stage tableau needs its y1 output for the tolerance")
-            b, cb, cf, ks = self._combo(spec, bufs, x)
-            err = (st.rows, (b, cb, cf, ks), bufs['Y'], 0 if L['y1'] is not None else -1, self.atol_f, self.rtol_f)
-        j = i + 1
-        f_out = bufs['K%d' % j] if (j in P.store or (mid and j in P.store_mid)) else None
+            err = (st.rows, err, bufs['Y'], err_y1, self.atol_f, self.rtol_f)
+        f_out = bufs['K%d' % (i + 1)] if store else None
         if lin:
             self.func.rhs_stage(t, x, ops.Stage(f_out=f_out, outs=outs, err=err, scale=st.scale,
                                                 f_lin=P.beta[0][0]), linear=True)
@@ -1609,20 +1262,6 @@ class _RKAdaptiveFused(_RKAdaptive):
         """The step-size controller runs on the device (a device solve with the
         default RMS norm): the host reads {ratio, dt, next dt} once per step."""
         return not self.host and 'norm' not in self.options
-
-    def _rotate(self, bufs, kn, d):
-        """Advance (d = 1) or undo (d = -1) the binding of y0 / f0 after an accepted
-        step: two buffers swap; with the third (steps ahead) the three rotate."""
-        P = self.plan
-        for a, b, c in (('Y', 'Y1', 'Ys'), ('K0', kn, 'Ks')):
-            if c not in bufs:
-                bufs[a], bufs[b] = bufs[b], bufs[a]
-            elif d > 0:
-                bufs[a], bufs[b], bufs[c] = bufs[b], bufs[c], bufs[a]
-            else:
-                bufs[a], bufs[b], bufs[c] = bufs[c], bufs[a], bufs[b]
-        if P.fsal:
-            bufs['X%d' % (P.ns - 1)] = bufs['Y1']
 
     def _rec_reader(self, st, rec, slot=None):
         """A device fp64 record (the step's {ratio, dt, next dt, e2}; h of the initial
@@ -1883,9 +1522,6 @@ class _RKAdaptiveFused(_RKAdaptive):
         t_cur = th[0]
         last = None  # (t_prev, dt) of the last accepted step
         self._dense = None
-        order = float(P.order)
-        safety, ifactor, dfactor = self.safety_f, self.ifactor_f, self.dfactor_f
-        kn = 'K%d' % P.ns
         dev_ctl = self._dev_control()
         if dev_ctl and not dt_on_device:  # the device controller carries dt (and the scale) from step to step
             st.dt.fill_(dt)
@@ -1911,10 +1547,7 @@ class _RKAdaptiveFused(_RKAdaptive):
         for i_out in range(1, len(th)):
             next_t = th[i_out]
             while next_t > t_cur:
-                if not (t_cur + dt > t_cur):
-                    raise AssertionError('underflow in dt {}'.format(dt))
-                if self.n_steps >= self.max_num_steps:
-                    raise AssertionError('max_num_steps exceeded ({}>={})'.format(self.n_steps, self.max_num_steps))
+                check_step(t_cur, dt, self.n_steps, self.max_num_steps)
                 mid = t_cur + dt >= next_t  # an accepted step would cross an output time: keep the dense-output k's
                 if pending is not None:
                     read, pending = pending, None
@@ -1928,7 +1561,7 @@ class _RKAdaptiveFused(_RKAdaptive):
                 # overwrites them); it keeps its own (mid variant: its dt is not known yet)
                 if spec_ok and st.warm and not mid and self.n_steps + 1 < self.max_num_steps and \
                         _nfe_headroom(self.func, 2 * P.ns):
-                    self._rotate(bufs, kn, 1)
+                    rotate(bufs, P, 1)
                     ahead = self._rec_reader(st, self._run_step(st, graphs_ok, t_cur + dt, dt, True))
                 # the step crossing next_t (steps-ahead mode, its k's kept): its dense output is
                 # enqueued before its record is read, so the pass follows the step on the device
@@ -1955,21 +1588,17 @@ class _RKAdaptiveFused(_RKAdaptive):
                     if ahead is not None:
                         pending = ahead  # already on the accepted binding
                     else:
-                        self._rotate(bufs, kn, 1)
+                        rotate(bufs, P, 1)
                 elif ahead is not None:  # rejected: discard the step ahead, step n again from its inputs
-                    self._rotate(bufs, kn, -1)
+                    rotate(bufs, P, -1)
                     st.dt.fill_(dt_next)
                     st.scale.fill_(dt_next)
                     st.tdev[0].fill_(t_cur)  # (the discarded step's controller may have advanced it)
                     if hasattr(self.func, 'nfe'):
                         self.func.nfe -= P.ns
-                if dt_next is not None:
-                    dt = dt_next
-                elif ratio == 0:
-                    dt = dt * ifactor
-                else:
-                    df = 1.0 if ratio < 1 else dfactor
-                    dt = dt * min(ifactor, max(safety / ratio ** (1.0 / order), df))
+                if dt_next is None:  # (the host controller; the device controller's record carries its own)
+                    dt_next = next_dt(dt, ratio, float(P.order), self.safety_f, self.ifactor_f, self.dfactor_f)
+                dt = dt_next
                 self.n_steps += 1
             if next_t == t_cur or last is None:
                 if self.host:
@@ -1995,13 +1624,7 @@ class _RKAdaptiveFused(_RKAdaptive):
             raise RuntimeError("gnpde: dense output of a step whose stage derivatives were not kept")
         y_prev, y_cur = d['Y'], d['Y1']
         f0, f1 = d['K0'], d['K%d' % P.ns]
-        x = (t - t0) / (t1 - t0)
-        x2, x3, x4 = x * x, x * x * x, x * x * x * x
-        cy0 = 1.0 - 11.0 * x2 + 18.0 * x3 - 8.0 * x4
-        cy1 = -5.0 * x2 + 14.0 * x3 - 8.0 * x4
-        cym = 16.0 * x2 - 32.0 * x3 + 16.0 * x4
-        cf0 = dt * (x - 4.0 * x2 + 5.0 * x3 - 2.0 * x4)
-        cf1 = dt * (x2 - 3.0 * x3 + 2.0 * x4)
+        wts = cy0, cy1, cym, cf0, cf1 = dense_weights((t - t0) / (t1 - t0), dt)
         rows = None if (lay is None or self.host) else lay.order32
         K = self.krylov
         if K is not None:
@@ -2011,40 +1634,15 @@ class _RKAdaptiveFused(_RKAdaptive):
                 c = cy1 * dt * K.G[p] + cym * dt * K.Mu[p] + (cf0 if p == 0 else 0.0)
                 if c != 0.0:
                     terms.append((d['K%d' % p], c))
-            stage = ops.Stage(outs=[(out, y_prev, cy0 + cy1 + cym, cym * dt * P.c_mid[P.ns] + cf1, terms)],
-                              out_rows=rows)
-            if self.host:
-                self.func.host_stage_apply(stage, f1, y_prev, y_prev)
-            else:
-                ops.stage_apply(stage, f1, y_prev, y_prev)
+            self._apply(ops.Stage(outs=[(out, y_prev, cy0 + cy1 + cym, cym * dt * P.c_mid[P.ns] + cf1, terms)],
+                                  out_rows=rows), f1, y_prev, y_prev)
             return
-        # one pass: out = (cy0 + cym) y0 + cy1 y1 + sum_j cym dt c_mid[j] k_j + cf0 f0 + cf1 f1
-        coef = {}  # id -> [tensor, coefficient] of the operands besides y0 (base) and f1 (f input)
-        order_ = []
-
-        def add(tn, c):
-            if c == 0.0:
-                return
-            if id(tn) not in coef:
-                coef[id(tn)] = [tn, 0.0]
-                order_.append(id(tn))
-            coef[id(tn)][1] += c
-        add(y_cur, cy1)
-        for j in range(P.ns + 1):
-            if _nz(P.c_mid[j]):
-                add(d['K%d' % j] if j < P.ns else f1, cym * dt * P.c_mid[j])
-        add(f0, cf0)
-        cf_f1 = coef.pop(id(f1))[1] + cf1 if id(f1) in coef else cf1
-        terms = [tuple(coef[k]) for k in order_ if k in coef]
-        if len(terms) <= _lib.STAGE_MAX_K and (not self.host or hasattr(self.func, 'host_stage_apply')):
-            stage = ops.Stage(outs=[(out, y_prev, cy0 + cym, cf_f1, terms)], out_rows=rows)
-            if self.host:
-                self.func.host_stage_apply(stage, f1, y_prev, y_prev)
-            else:
-                ops.stage_apply(stage, f1, y_prev, y_prev)
+        cb, cf_f1, terms = dense_combo(P, wts, dt, y_cur, f0, f1, lambda j: d['K%d' % j])
+        if len(terms) <= _lib.STAGE_MAX_K:
+            self._apply(ops.Stage(outs=[(out, y_prev, cb, cf_f1, terms)], out_rows=rows), f1, y_prev, y_prev)
             return
         ymid = torch.empty_like(out)
-        mterms = [(d['K%d' % j], dt * P.c_mid[j]) for j in range(P.ns + 1) if _nz(P.c_mid[j])]
+        mterms = [(d['K%d' % j], dt * P.c_mid[j]) for j in range(P.ns + 1) if P.c_mid[j] != 0.0]
         self._apply(ops.Stage(outs=[(ymid, y_prev, 1.0, 0.0, mterms)]), None, None, y_prev)
         self._apply(ops.Stage(outs=[(out, y_prev, cy0, 0.0, [(y_cur, cy1), (ymid, cym), (f0, cf0), (f1, cf1)])],
                               out_rows=rows), None, None, y_prev)
@@ -2134,24 +1732,12 @@ def _laplacian_aug(func, params, y_shape, ny, ans):
     parameters' components are 0.  For the adaptive adjoint methods (torchdiffeq's
     solver loop, the mixed norm); the fixed-grid rk4 adjoint runs _LaplacianAdjointFn.
     None when the RHS is not the HIP Laplacian on a device fp32 state."""
-    fn = getattr(func, 'adjoint_direct_ok', None)
-    if not (FUSED_ADJOINT and fn is not None and fn(params) and hasattr(func, 'rhs_stage')) or \
-            func.opt.get('no_alpha_sigmoid', False) or not ans.is_cuda or ans.dtype != torch.float32 or \
-            len(y_shape) != 3:
+    if not (FUSED_ADJOINT and ans.is_cuda and ans.dtype == torch.float32 and len(y_shape) == 3 and
+            laplacian_adjoint_ok(func, params)):
         return None
-    own = {id(p) for p in func.parameters()}
-    if not all(id(p) in own for p in params):
-        return None
-    y0 = ans[0]
-    g = func.graph_for(y0)
-    w, tag = func._weights_tensor()
-    w_csr = func.csr_weights(g, w, tag)
-    w_csc = g.gather_weights(w.detach().float() if w.dtype != torch.float32 else w.detach(), transpose=True)
-    add_source = bool(func.opt.get('add_source', False))
-    x0 = func.stable_x0(y0) if add_source else None
-    alpha, beta = func.alpha_train.detach(), func.beta_train.detach()
-    R = y0.numel() // y0.shape[-1]
-    drow = torch.empty(R, dtype=torch.float64, device=y0.device)
+    o = laplacian_operands(func, ans[0], csr=True, private_csc=True, acc=0, acc_zero=False)
+    g, w_csr, w_csc, add_source, x0, alpha, beta, drow = (o.g, o.w_csr, o.w_csc, o.add_source, o.x0, o.alpha, o.beta,
+                                                          o.acc)
     slots = {}
     o = 2 * ny
     for p in params:
@@ -2174,8 +1760,7 @@ def _laplacian_aug(func, params, y_shape, ny, ans):
         out[2 * ny:].zero_()
         if id(func.alpha_train) in slots:
             oa, _ = slots[id(func.alpha_train)]
-            ga = ops.sum_f64(drow) * (1.0 - torch.sigmoid(alpha.double()))
-            out[oa:oa + 1].copy_(ga.reshape(1))
+            out[oa:oa + 1].copy_(alpha_grad(drow, alpha.double()).reshape(1))
         if add_source and id(func.beta_train) in slots:
             ob, _ = slots[id(func.beta_train)]
             out[ob:ob + 1].copy_(ops.dot(a, x0).reshape(1))
@@ -2196,11 +1781,7 @@ def _adaptive_adjoint_ok(func, ans, a_method, params, a_options):
         return False
     if not (ans.is_cuda and ans.dtype == torch.float32 and ans.dim() == 4):
         return False
-    fn = getattr(func, 'adjoint_direct_ok', None)
-    if fn is None or not fn(params) or func.opt.get('no_alpha_sigmoid', False) or not hasattr(func, 'rhs_stage'):
-        return False
-    own = {id(p) for p in func.parameters()}
-    return all(id(p) in own for p in params)
+    return laplacian_adjoint_ok(func, params)
 
 
 class _OdeintAdjoint(torch.autograd.Function):
@@ -2230,16 +1811,11 @@ class _OdeintAdjoint(torch.autograd.Function):
         if _adaptive_adjoint_ok(func, ans, a_method, params, a_options):
             # the Laplacian's adaptive adjoint, fused (gnpde.adjoint_adaptive): the same loop with the
             # packed state's stage combinations, error rows and alpha integrand in the K1 epilogues
-            from .adjoint_adaptive import AdaptiveAdjoint
             with torch.no_grad():
                 solver = AdaptiveAdjoint(func, params, a_method, a_rtol, a_atol, a_options)
-                gy, pg = solver.run(_host_times(t), ans, grad_y)
+                gy, ga, gb = solver.run(_host_times(t), ans, grad_y)
             _OdeintAdjoint.last_path = 'fused_adaptive'
-            out = []
-            for p in params:
-                v = pg.get(id(p))
-                out.append(torch.zeros_like(p) if v is None else
-                           torch.full(p.shape, v, dtype=p.dtype, device=p.device))
+            out = param_grads(params, [(func.alpha_train, ga), (func.beta_train, gb)])
             return (gy.view(grad_y.shape[1:]).to(grad_y.dtype), None, None) + tuple(out)
         y_shape = ans.shape[1:]
         ny = ans[0].numel()
@@ -2328,12 +1904,7 @@ def _fused_adjoint_ok(func, y0, adjoint_method, adjoint_params):
     if not (FUSED_ADJOINT and adjoint_method == 'rk4' and y0.is_cuda and y0.dtype == torch.float32 and
             y0.dim() == 3):
         return False
-    fn = getattr(func, 'adjoint_direct_ok', None)
-    if fn is None or not fn(adjoint_params) or func.opt.get('no_alpha_sigmoid', False) or \
-            not hasattr(func, 'rhs_stage'):
-        return False
-    own = {id(p) for p in func.parameters()}
-    return all(id(p) in own for p in adjoint_params)
+    return laplacian_adjoint_ok(func, adjoint_params)
 
 
 class _LaplacianAdjointFn(torch.autograd.Function):
@@ -2375,16 +1946,10 @@ class _LaplacianAdjointFn(torch.autograd.Function):
             if lay is not None:
                 func._layout = lay
             try:
-                gr = func.graph_for(ans[0])
-                w, tag = func._weights_tensor()
-                w_csc = gr.gather_weights(w.detach().float() if w.dtype != torch.float32 else w.detach(),
-                                          transpose=True)
-                R = ans[0].numel() // ans[0].shape[-1]
-                acc = torch.zeros(1 + R, dtype=torch.float64, device=ans.device)
-                gb, drow = acc[0], acc[1:]
-                add_source = bool(func.opt.get('add_source', False))
-                x0 = func.stable_x0(ans[0]) if add_source else None
-                arhs = _AdjointRHS(gr, w_csc, func.alpha_train.detach(), True, drow)
+                o = laplacian_operands(func, ans[0], private_csc=True, acc=1)
+                gb, drow = o.acc[0], o.acc[1:]
+                add_source, x0 = o.add_source, o.x0
+                arhs = _AdjointRHS(o.g, o.w_csc, o.alpha, True, drow)
                 step = a_options.get('step_size')
 
                 def internal(v):
@@ -2415,8 +1980,7 @@ class _LaplacianAdjointFn(torch.autograd.Function):
                                 gb = gb + (c * h / 8.0) * ops.dot(av, x0)
                         y, a = yo, ao
                     a = a + internal(grad_y[i - 1])
-                sig = torch.sigmoid(func.alpha_train.detach()).double()
-                ga = ops.sum_f64(drow) * (1.0 - sig)
+                ga = alpha_grad(drow, o.alpha)
                 if lay is not None:
                     gy = torch.empty_like(a)
                     _to_user(a, gy, lay)
@@ -2424,14 +1988,7 @@ class _LaplacianAdjointFn(torch.autograd.Function):
                     gy = a
             finally:
                 func._layout = None
-        out = []
-        for p in params:
-            if p is func.alpha_train:
-                out.append(ga.to(p.dtype).reshape(p.shape))
-            elif p is func.beta_train and add_source:
-                out.append(gb.to(p.dtype).reshape(p.shape))
-            else:
-                out.append(torch.zeros_like(p))
+        out = param_grads(params, [(func.alpha_train, ga), (func.beta_train, gb if add_source else None)])
         return (gy.view(grad_y.shape[1:]), None, None) + tuple(out)
 
 

@@ -31,12 +31,15 @@ def relerr(a, b):
     return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
 
 
-def _run(fused, monkeypatch, method, add_source, t, first_step, tol=1e-4):
-    N, E, C = 2500, 20000, 32
+def _run(fused, monkeypatch, method, add_source, t, first_step, tol=1e-4, size=(2500, 20000, 32), hub=400,
+         between=None, backward=True):
+    """One solve and its backward.  ``between(func, xt, tt, rng)`` runs after the forward and
+    before the backward; backward=False returns (loss, func) instead of the gradients."""
+    N, E, C = size
     rng = np.random.default_rng(91)
     ei = torch.from_numpy(rng.integers(0, N, size=(1, 2, E))).to(DEV)
-    ei[:, 0, :400] = 3  # hub row (CSR split plan)
-    ei[:, 1, 400:800] = 8  # hub column (CSC split plan)
+    ei[:, 0, :hub] = 3  # hub row (CSR split plan)
+    ei[:, 1, hub:2 * hub] = 8  # hub column (CSC split plan)
     w = torch.from_numpy(rng.uniform(0.05, 0.3, size=(1, E)).astype(np.float32)).to(DEV)
     x = torch.from_numpy(rng.standard_normal((1, N, C)).astype(np.float32)).to(DEV)
     x0 = torch.from_numpy(rng.standard_normal((1, N, C)).astype(np.float32)).to(DEV)
@@ -56,6 +59,10 @@ def _run(fused, monkeypatch, method, add_source, t, first_step, tol=1e-4):
     z = gnpde.odeint(func, xt, tt, method=method, rtol=tol * 1e-2, atol=tol, options={'first_step': first_step})
     path = gi.odeint.last_path
     steps = gi.odeint.last_n_steps
+    if between is not None:
+        between(func, xt, tt, rng)
+    if not backward:
+        return (z * R).sum(), func
     (z * R).sum().backward()
     return dict(z=z.detach(), x=xt.grad, alpha=func.alpha_train.grad, beta=func.beta_train.grad, w=wt.grad,
                 nfe=func.nfe, steps=steps, path=path)
@@ -122,3 +129,53 @@ def test_cora_attention_block_training_step(monkeypatch):
     for name, u, v in zip(("z", "x", "alpha", "beta", "Q", "K"), a[:6], b[:6]):
         assert u is not None and v is not None, name
         assert relerr(u, v) <= 1e-5, (name, relerr(u, v))
+
+
+# The node keeps what its backward reads: N = 600, E = 5000, C = 32, hubs of 300 edges (longer than the
+# small-graph chunk of 16 in the CSR and the CSC plan), dopri5 over [0, 0.55, 1.6] with add_source.
+SMALL = dict(method='dopri5', add_source=True, t=[0.0, 0.55, 1.6], first_step=0.05, size=(600, 5000, 32), hub=300)
+
+
+def _perturb(func, xt, tt, rng):
+    """Everything a backward that read the module late would see changed: new weights and x0
+    tensors, a no_grad solve that refreshes the module's cached CSR / CSC buffers and stable
+    x0 in place, and a new edge_index (the columns permuted: another graph object)."""
+    func.edge_weight = (3 * func.edge_weight).detach()
+    func.x0 = torch.from_numpy(rng.standard_normal(tuple(func.x0.shape)).astype(np.float32)).to(DEV)
+    with torch.no_grad():
+        gnpde.odeint(func, xt.detach(), tt, method='dopri5', rtol=1e-6, atol=1e-4, options={'first_step': 0.05})
+    perm = torch.from_numpy(rng.permutation(func.edge_index.shape[-1])).to(DEV)
+    func.edge_index = func.edge_index[:, :, perm].contiguous()
+
+
+def test_backprop_node_reads_the_state_its_forward_took(monkeypatch):
+    """Gradients of a forward whose module is changed before its backward equal those of the
+    undisturbed run: within 1e-6 of each gradient's largest entry, the bar two undisturbed
+    runs are first held to (the node's own repeatability)."""
+    ref = _run(True, monkeypatch, **SMALL)
+    again = _run(True, monkeypatch, **SMALL)
+    late = _run(True, monkeypatch, between=_perturb, **SMALL)
+    assert ref['path'] == late['path'] == 'fused_backprop' and ref['steps'] == late['steps']
+    for k in ('x', 'alpha', 'beta', 'w'):
+        print(k, 'repeat', relerr(again[k], ref[k]), 'perturbed', relerr(late[k], ref[k]))
+    for k in ('x', 'alpha', 'beta', 'w'):
+        assert relerr(again[k], ref[k]) <= 1e-6, (k, relerr(again[k], ref[k]))
+    for k in ('x', 'alpha', 'beta', 'w'):
+        assert relerr(late[k], ref[k]) <= 1e-6, (k, relerr(late[k], ref[k]))
+
+
+def test_backprop_node_refuses_a_parameter_edited_in_place(monkeypatch):
+    """alpha_train is saved with the node: an in-place edit between forward and backward is
+    autograd's error, not a silently different gradient."""
+    loss, func = _run(True, monkeypatch, backward=False, **SMALL)
+    with torch.no_grad():
+        func.alpha_train.add_(0.1)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        loss.backward()
+
+
+def test_backprop_node_second_backward_says_buffers_were_released(monkeypatch):
+    loss, _func = _run(True, monkeypatch, backward=False, **SMALL)
+    loss.backward(retain_graph=True)
+    with pytest.raises(RuntimeError, match="released after its first backward"):
+        loss.backward(retain_graph=True)

@@ -528,3 +528,127 @@ def test_dense_fold_table_matches_host_interpolant(method):
         p2 = dt * (f1 - 4 * u[0]) - 11 * y0 - 5 * y1 + 16 * ymid
         quartic = y0 + theta * (dt * u[0]) + x2 * p2 + x3 * p3 + x4 * p4
         assert np.allclose(dense, quartic, rtol=1e-12, atol=1e-12)
+
+
+# ---------------------------------------------------------------- what the adaptive loops share (gnpde.solver_common)
+@pytest.mark.parametrize("method", list(gode.ADAPTIVE_METHODS))
+def test_dense_weights_and_combo_match_the_tableau_interpolant(method):
+    """dense_weights + dense_combo (the one-pass dense output of the fused solver and the
+    adaptive adjoint) against _RKAdaptive._interp on the same y0, y1 and k_j, in fp64.
+    1e-12 of the largest entry: fp64 sums of fewer than 20 terms of size O(10), re-associated.
+    At x = 0 the result is y0 itself."""
+    from gnpde import solver_common as sc
+    P = sc._adaptive_plan(method)
+    rng = np.random.default_rng(3)
+    y0, y1 = (torch.from_numpy(rng.standard_normal((1, 7, 3))) for _ in range(2))
+    k = [torch.from_numpy(rng.standard_normal((1, 7, 3))) for _ in range(P.ns + 1)]
+    solver = gode._RKAdaptive(None, y0, 1e-6, 1e-8, gode._torch_combine, method=method)
+    t0, dt = 0.4, 0.7
+    for x in (0.0, 0.3, 1.0):
+        want = solver._interp(y0, y1, k, dt, t0, t0 + dt, t0 + x * dt)
+        base, cf, terms = sc.dense_combo(P, sc.dense_weights(x, dt), dt, y1, k[0], k[-1], lambda j: k[j])
+        got = base * y0 + cf * k[-1] + sum(c * tn for tn, c in terms)
+        assert all(tn is not k[-1] for tn, _ in terms)  # f1 is the pass's f input, never an operand too
+        assert len({id(tn) for tn, _ in terms}) == len(terms)
+        assert float((got - want).abs().max()) <= 1e-12 * float(want.abs().max()), (method, x)
+        if x == 0.0:
+            assert torch.equal(got, y0)
+
+
+@pytest.mark.parametrize("order", [2, 3, 5])
+def test_next_dt_matches_the_tensor_controller(order):
+    """next_dt (host floats) against _RKAdaptive._optimal_step_size (fp64 tensors): 1e-14
+    relative, two roundings of pow."""
+    from gnpde import solver_common as sc
+    method = {2: 'adaptive_heun', 3: 'bosh3', 5: 'dopri5'}[order]
+    solver = gode._RKAdaptive(None, torch.zeros(1, 2, 2, dtype=torch.float64), 1e-6, 1e-8, gode._torch_combine,
+                              method=method)
+    assert solver.order == order
+    dt = 0.37
+    for ratio in (0.0, 1e-12, 0.5, 1.0, 4.0, 1e6):
+        want = float(solver._optimal_step_size(torch.tensor(dt, dtype=torch.float64),
+                                               torch.tensor(ratio, dtype=torch.float64)))
+        got = sc.next_dt(dt, ratio, float(order), 0.9, 10.0, 0.2)
+        assert abs(got - want) <= 1e-14 * abs(want), (ratio, got, want)
+
+
+def test_check_step_messages():
+    from gnpde import solver_common as sc
+    sc.check_step(0.0, 0.1, 3, 4)
+    with pytest.raises(AssertionError, match=r"underflow in dt 1e-30"):
+        sc.check_step(1.0, 1e-30, 0, 10)
+    with pytest.raises(AssertionError, match=r"max_num_steps exceeded \(4>=4\)"):
+        sc.check_step(0.0, 0.1, 4, 4)
+
+
+@pytest.mark.parametrize("method", list(gode.ADAPTIVE_METHODS))
+def test_plan_launch_matches_the_loops_it_replaced(method):
+    """_AdaptivePlan.launch / .combo, resolved with symbol -> its own name, against a literal
+    transcription of the loop the three solvers each carried: the same (dst, base, cb, cf,
+    terms) tuples, error combination, err_y1 flag and f_out decision for every launch, with
+    the device-scaled coefficients (mult 1) and the host-dt ones (adaptive backprop)."""
+    from gnpde import solver_common as sc
+    P = sc._adaptive_plan(method)
+
+    def combo(spec, dt):
+        base, terms, cfc = spec
+        bt = {'Y': 'Y', 'X': 'X', 'E': 'E', None: None}[base]
+        return bt, (1.0 if bt is not None else 0.0), cfc * dt, [(k, c * dt) for k, c in terms]
+
+    for i in range(P.ns):
+        for mid in (False, True):
+            for dt in (1.0, 0.3):
+                L = P.launches[i]
+                outs = []
+                for key, dst in (('next', 'X%d' % (i + 1)), ('y1', 'Y1'), ('epart', 'E')):
+                    if L[key] is not None:
+                        bt, cb, cf, ks = combo(L[key], dt)
+                        outs.append((dst, bt, cb, cf, ks))
+                err = combo(L['err'], dt) if L['err'] is not None else None
+                j = i + 1
+                store = j in P.store or (mid and j in P.store_mid)
+                got = P.launch(i, mid, lambda s: s, mult=dt)
+                assert got == (outs, err, 0 if L['y1'] is not None else -1, store), (method, i, mid, dt)
+                names = {s: s for s in ['Y', 'X', 'E', 'Y1'] + ['K%d' % q for q in range(P.ns + 1)] +
+                         ['X%d' % q for q in range(P.ns + 1)]}
+                assert P.launch(i, mid, names, mult=dt) == got  # a mapping serves as well as a callable
+    # a restated spec (the fused solver's affine first launch) is resolved in place of the plan's
+    outs, _err, _y1, _st = P.launch(0, False, lambda s: s, restate=lambda spec: ('Y', [('K0', 2.0)], spec[2]))
+    assert all(o[1] == 'Y' and o[4] == [('K0', 2.0)] for o in outs)
+
+
+def test_rotate_two_and_three_buffers():
+    from gnpde import solver_common as sc
+    P = sc._adaptive_plan('dopri5')
+    b = {'Y': 'a', 'Y1': 'b', 'K0': 'c', 'K6': 'd', 'X5': 'b'}
+    sc.rotate(b, P)
+    assert (b['Y'], b['Y1'], b['K0'], b['K6'], b['X5']) == ('b', 'a', 'd', 'c', 'a')
+    sc.rotate(b, P)
+    assert (b['Y'], b['Y1'], b['K0'], b['K6'], b['X5']) == ('a', 'b', 'c', 'd', 'b')
+    b.update(Ys='e', Ks='f')
+    sc.rotate(b, P, 1)
+    assert (b['Y'], b['Y1'], b['Ys'], b['K0'], b['K6'], b['Ks'], b['X5']) == ('b', 'e', 'a', 'd', 'f', 'c', 'e')
+    sc.rotate(b, P, -1)
+    assert (b['Y'], b['Y1'], b['Ys'], b['K0'], b['K6'], b['Ks'], b['X5']) == ('a', 'b', 'e', 'c', 'd', 'f', 'b')
+
+
+def test_solver_modules_import_without_a_cycle():
+    """The shared module imports neither the integrator nor the two solver modules, and
+    those two import no integrator (they are imported by it at top level)."""
+    import ast
+    import os
+    pkg = os.path.dirname(gode.__file__)
+    for name in ('solver_common', 'adaptive_backprop', 'adjoint_adaptive'):
+        tree = ast.parse(open(os.path.join(pkg, name + '.py')).read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom):
+                mods = [node.module or ''] + [a.name for a in node.names]
+            elif isinstance(node, ast.Import):
+                mods = [a.name for a in node.names]
+            else:
+                continue
+            assert not any(m.split('.')[-1] == 'integrator' for m in mods), (name, mods)
+    tree = ast.parse(open(os.path.join(pkg, 'integrator.py')).read())
+    lazy = [n for f in ast.walk(tree) if isinstance(f, (ast.FunctionDef, ast.Lambda))
+            for n in ast.walk(f) if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert not lazy
