@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "scores.hpp"
 
 namespace gnpde {
 
@@ -96,6 +97,76 @@ struct RefDstSoftmaxWeights {
     return acc / (float)H;
   }
 };
+
+// GAT attention (function_GAT_attention.py:131-135), head mean taken on the fly:
+// the score of edge (row, c) is LeakyReLU(sl[row,h] + sr[c,h]) from the node-score
+// pairs sp [R, 2H] = [sl | sr] (gnpde_gat_scores_f32); the softmax group g is the
+// row (DST false, attention_norm_idx 0) or the destination c (DST true, norm_idx 1).
+// load() issues the sr[c,:] gather and, with DST, the destination's statistics;
+// for source groups the row's own sl, m, rl are per-item values read in finish()
+// (one address per row slot: served by the cache).  Same arithmetic, in the same
+// order, as attn_weights_kernel in mode GAT (ScoreArgs::score -> gat_leaky), so the
+// fused launch equals the weights pass + the plain K1 bit for bit.
+// MAXH > 0: heads <= MAXH, operands loaded up front; MAXH == 0: any heads <= 8,
+// loaded in finish().
+template <int MAXH, bool DST>
+struct GatSoftmaxWeights {
+  const double* __restrict__ sp;
+  const double* __restrict__ m;
+  const float* __restrict__ rl;
+  int H;
+  float slope;
+  struct Raw {
+    double sr[MAXH > 0 ? MAXH : 1];
+    double mm[(MAXH > 0 && DST) ? MAXH : 1];
+    float rr[(MAXH > 0 && DST) ? MAXH : 1];
+    int c;
+  };
+  __device__ __forceinline__ Raw load(int /*row*/, int /*p*/, int c) const {
+    Raw r;
+    r.c = c;
+    if constexpr (MAXH > 0) {
+#pragma unroll
+      for (int h = 0; h < MAXH; ++h) {
+        const int hh = h < H ? h : 0;
+        r.sr[h] = sp[(int64_t)c * 2 * H + H + hh];
+        if constexpr (DST) {
+          r.mm[h] = m[(int64_t)c * H + hh];
+          r.rr[h] = rl[(int64_t)c * H + hh];
+        }
+      }
+    }
+    return r;
+  }
+  __device__ __forceinline__ float finish(int row, const Raw& r) const {
+    float acc = 0.f;
+    const int64_t g = DST ? r.c : row;
+    if constexpr (MAXH > 0) {
+#pragma unroll
+      for (int h = 0; h < MAXH; ++h)
+        if (h < H) {
+          const double s = gat_leaky(sp[(int64_t)row * 2 * H + h], r.sr[h], slope);
+          const double mg = DST ? r.mm[h] : m[g * H + h];
+          const float rg = DST ? r.rr[h] : rl[g * H + h];
+          acc += expf((float)(s - mg)) * rg;
+        }
+    } else {
+      for (int h = 0; h < H; ++h) {
+        const double s = gat_leaky(sp[(int64_t)row * 2 * H + h], sp[(int64_t)r.c * 2 * H + H + h], slope);
+        acc += expf((float)(s - m[g * H + h])) * rl[g * H + h];
+      }
+    }
+    return acc / (float)H;
+  }
+};
+
+// Policies that take the narrow-row lane geometries of launch_agg_vec (several rows per
+// wavefront below 17 lanes): the plain weights, and the GAT policy, which promises the
+// bits of the weights pass + the plain K1 at every width, so it sums in the same order.
+template <class WP>
+struct takes_narrow_rows : std::is_same<WP, PlainWeights> {};
+template <int MAXH, bool DST>
+struct takes_narrow_rows<GatSoftmaxWeights<MAXH, DST>> : std::true_type {};
 
 template <class WP>
 __host__ __device__ inline PlainWeights as_plain(const WP& wp) {
@@ -590,9 +661,9 @@ static int launch_agg_vec(const int4* items, int64_t n_items, int4* heavy, int64
   // 32 / 64 columns 2.06 / 3.67 ms against 2.56 / 4.52); a cache-resident one (G-arxiv
   // stripes) prefers several edge groups per row (0.149 / 0.124 ms at 32 / 16 columns
   // against 0.283 / 0.318).
-  // (plain weights only: the attention-weight policies take the 16-lane geometry for
-  // narrow rows, which keeps the library's instantiation count down)
-  if constexpr (std::is_same<WP, PlainWeights>::value) {
+  // (plain weights and the GAT policy, takes_narrow_rows: the reference-score policy takes
+  // the 16-lane geometry for narrow rows, which keeps the library's instantiation count down)
+  if constexpr (takes_narrow_rows<WP>::value) {
     if (var != 5) {
       if (n_items * (int64_t)C * (int64_t)sizeof(T) > (int64_t)(96 << 20)) {
         if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 16);

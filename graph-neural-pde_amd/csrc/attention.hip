@@ -166,10 +166,20 @@ constexpr int kSegLongMax = kWave * kSegLongU;  // 512: one pass
 // max-then-sum reductions instead of merging online pairs: hub / long groups 10.6 /
 // 6.9 us, but the scores kept in registers between the phases cost the short
 // items their occupancy, 22.7 us in all; reloading them, 20.2 us.)
-template <int U, int MAXH>
-__device__ __forceinline__ void load_cs_rows(const ScoreArgs& sa, const int (&src)[U], double (&v)[U][MAXH]) {
+// GAT (mode GNPDE_SCORE_GAT): the edge score of both endpoints' node scores — src[u] is
+// the other endpoint of group grp[u] (a destination group when gid, else a source group).
+template <int U, int MAXH, bool GAT = false>
+__device__ __forceinline__ void load_cs_rows(const ScoreArgs& sa, const int (&src)[U], double (&v)[U][MAXH],
+                                             const int (&grp)[U], int gid) {
   const int H = sa.H;
-  if constexpr (MAXH == 2) {  // launch_ref_stats: MAXH == 2 means H == 2 and 16-byte aligned rows
+  if constexpr (GAT) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int o = max(src[u], 0);
+#pragma unroll
+      for (int h = 0; h < MAXH; ++h) v[u][h] = h < H ? (gid ? sa.score(o, grp[u], h) : sa.score(grp[u], o, h)) : 0.0;
+    }
+  } else if constexpr (MAXH == 2) {  // launch_ref_stats: MAXH == 2 means H == 2 and 16-byte aligned rows
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const double2 t = *reinterpret_cast<const double2*>(sa.cs + (int64_t)max(src[u], 0) * 2);
@@ -184,18 +194,20 @@ __device__ __forceinline__ void load_cs_rows(const ScoreArgs& sa, const int (&sr
   }
 }
 
-template <int U, int MAXH>
+template <int U, int MAXH, bool GAT = false>
 __device__ __forceinline__ void push_edges(int pb, int stride, int e1, const int* __restrict__ gidx,
-                                           const ScoreArgs& sa, double (&M)[MAXH], float (&L)[MAXH]) {
+                                           const ScoreArgs& sa, double (&M)[MAXH], float (&L)[MAXH], int grp = 0,
+                                           int gid = 1) {
   const int H = sa.H;
-  int src[U];
+  int src[U], gr[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int p = pb + stride * u;
     src[u] = p < e1 ? gidx[p] : -1;
+    gr[u] = grp;
   }
   double v[U][MAXH];
-  load_cs_rows<U, MAXH>(sa, src, v);
+  load_cs_rows<U, MAXH, GAT>(sa, src, v, gr, gid);
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -209,9 +221,9 @@ __device__ __forceinline__ void wave_merge(double (&M)[MAXH], float (&L)[MAXH]) 
 }
 
 // at most kSegLongMax edges [e0, e1) by one wavefront: (M, L) per head, every lane
-template <int MAXH>
+template <int MAXH, bool GAT = false>
 __device__ __forceinline__ void long_item_stats(int e0, int e1, const int* __restrict__ gidx, const ScoreArgs& sa,
-                                                double (&M)[MAXH], float (&L)[MAXH]) {
+                                                double (&M)[MAXH], float (&L)[MAXH], int grp = 0, int gid = 1) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int h = 0; h < MAXH; ++h) {
@@ -223,22 +235,24 @@ __device__ __forceinline__ void long_item_stats(int e0, int e1, const int* __res
 #pragma unroll(MAXH <= 2 ? kSegLongU / LU : 1)
   for (int ps = 0; ps < kSegLongU / LU; ++ps) {
     if (e0 + ps * LU * kWave >= e1) break;  // wave-uniform: an item of fewer edges skips the empty passes
-    push_edges<LU, MAXH>(e0 + lane + ps * LU * kWave, kWave, e1, gidx, sa, M, L);
+    push_edges<LU, MAXH, GAT>(e0 + lane + ps * LU * kWave, kWave, e1, gidx, sa, M, L, grp, gid);
   }
   if (GNPDE_EXPERIMENTS && rs_skip() == 4) return;
   wave_merge<MAXH>(M, L);
 }
 
 // a hub chunk: partials write-through, arrival ticket, the last arrival merges
-template <int MAXH>
+template <int MAXH, bool GAT = false>
 __device__ __forceinline__ void hub_chunk_stats(int e0, int e1, int slot, int hub, const int* __restrict__ gidx,
                                                 const ScoreArgs& sa, int4* heavy, double* __restrict__ partials,
-                                                double* m, float* rl, float* mr) {
+                                                double* m, float* rl, float* mr, int gid = 1) {
   const int lane = threadIdx.x & 63;
   const int H = sa.H;
   double M[MAXH];
   float L[MAXH];
-  long_item_stats<MAXH>(e0, e1, gidx, sa, M, L);
+  int grp = 0;
+  if constexpr (GAT) grp = uniform(heavy[hub].x);  // the hub's group: its own node scores
+  long_item_stats<MAXH, GAT>(e0, e1, gidx, sa, M, L, grp, gid);
   const __amdgpu_buffer_rsrc_t rp = buf_rsrc(partials);
   const int64_t pb = (int64_t)slot * 2 * H;
 #pragma unroll
@@ -370,12 +384,14 @@ __global__ __launch_bounds__(256) void seg_softmax_kernel(const int4* __restrict
 // round 4 (256-thread workgroups, hub chunks) 16.25 / 16.9 / 19.1 us (tools/ab_stats.sh)
 constexpr int kRefStatsNI = GNPDE_RS_NI;
 
-template <int NI, int MAXH>
+// GAT: the scores of mode GNPDE_SCORE_GAT (both endpoints' node scores) over the groups of
+// either grouping (gid: destination groups); the reference instantiations are unchanged.
+template <int NI, int MAXH, bool GAT = false>
 __global__ __launch_bounds__(256) void ref_stats_kernel(const int4* __restrict__ items, int n_items, int n_hub,
                                                          int n_long, const int* __restrict__ rowidx,
                                                          const int* __restrict__ gidx, ScoreArgs sa, int4* heavy,
                                                          double* __restrict__ partials, double* __restrict__ m,
-                                                         float* __restrict__ rl, float* __restrict__ mr) {
+                                                         float* __restrict__ rl, float* __restrict__ mr, int gid) {
   const int lane = threadIdx.x & 63;
   const int wid = uniform((int)blockIdx.x * kWavesPerBlock + (int)(threadIdx.x >> 6));
   if constexpr (GNPDE_EXPERIMENTS) {  // timing probes: 1 skips the hub / long items, 2 the short ones
@@ -390,13 +406,13 @@ __global__ __launch_bounds__(256) void ref_stats_kernel(const int4* __restrict__
       return;
     }
     if (wid < n_hub) {
-      hub_chunk_stats<MAXH>(uniform(it.x), uniform(it.y), uniform(it.z), uniform(it.w), gidx, sa, heavy, partials, m,
-                            rl, mr);
+      hub_chunk_stats<MAXH, GAT>(uniform(it.x), uniform(it.y), uniform(it.z), uniform(it.w), gidx, sa, heavy, partials,
+                                 m, rl, mr, gid);
       return;
     }
     double M[MAXH];
     float L[MAXH];
-    long_item_stats<MAXH>(uniform(it.x), uniform(it.y), gidx, sa, M, L);
+    long_item_stats<MAXH, GAT>(uniform(it.x), uniform(it.y), gidx, sa, M, L, uniform(it.w), gid);
     if (lane == 0)
 #pragma unroll
       for (int h = 0; h < MAXH; ++h)
@@ -420,7 +436,7 @@ __global__ __launch_bounds__(256) void ref_stats_kernel(const int4* __restrict__
     src[i] = n[i] > 0 ? gidx[p] : 0;
   }
   double v[NI][MAXH];
-  load_cs_rows<NI, MAXH>(sa, src, v);
+  load_cs_rows<NI, MAXH, GAT>(sa, src, v, grp, gid);
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     if (n[i] > 0) {  // wave-uniform
@@ -446,7 +462,7 @@ __global__ __launch_bounds__(256) void ref_stats_kernel(const int4* __restrict__
 template <int NI>
 static int launch_ref_stats(const int4* items, int64_t n_items, int64_t n_hub, int64_t n_long, const int* rowidx,
                             const int* gidx, const ScoreArgs& sa, int4* heavy, double* partials, double* m, float* rl,
-                            float* mr, hipStream_t s) {
+                            float* mr, hipStream_t s, int gid = 1) {
 #if GNPDE_EXPERIMENTS
   static const bool once = [] {  // GNPDE_RS_SKIP: the kernel's timing probes (before any capture)
     const char* e = std::getenv("GNPDE_RS_SKIP");
@@ -459,8 +475,20 @@ static int launch_ref_stats(const int4* items, int64_t n_items, int64_t n_hub, i
   const unsigned grid = (unsigned)ceil_div(waves, (int64_t)kWavesPerBlock);
 #define GNPDE_RS(M)                                                                                            \
   ref_stats_kernel<NI, M><<<grid, kBlock, 0, s>>>(items, (int)n_items, (int)n_hub, (int)n_long, rowidx, gidx, sa, \
-                                                   heavy, partials, m, rl, mr)
-  if (sa.H <= 1)
+                                                   heavy, partials, m, rl, mr, 1)
+#define GNPDE_RS_GAT(M)                                                                                      \
+  ref_stats_kernel<NI, M, true><<<grid, kBlock, 0, s>>>(items, (int)n_items, (int)n_hub, (int)n_long, rowidx, gidx, \
+                                                         sa, heavy, partials, m, rl, mr, gid)
+  if (sa.mode == GNPDE_SCORE_GAT) {
+    if (sa.H <= 1)
+      GNPDE_RS_GAT(1);
+    else if (sa.H <= 2)
+      GNPDE_RS_GAT(2);
+    else if (sa.H <= 4)
+      GNPDE_RS_GAT(4);
+    else
+      GNPDE_RS_GAT(8);
+  } else if (sa.H <= 1)
     GNPDE_RS(1);
   else if (sa.H <= 2 && aligned16(sa.cs))  // MAXH 2: two heads, 16-byte node-score rows
     GNPDE_RS(2);
@@ -470,6 +498,7 @@ static int launch_ref_stats(const int4* items, int64_t n_items, int64_t n_hub, i
     GNPDE_RS(8);
   else
     GNPDE_RS(16);
+#undef GNPDE_RS_GAT
 #undef GNPDE_RS
   GNPDE_LAUNCH_CHECK();
   return GNPDE_OK;
@@ -500,7 +529,7 @@ int gnpde_seg_long_edges(void) { return kSegLongMax; }
 int gnpde_seg_long_pass_edges(int64_t heads) { return kWave * (heads <= 2 ? kSegLongU : 2); }
 
 int gnpde_seg_block_edges(int mode, int64_t heads, int64_t dk) {
-  if (mode == GNPDE_SCORE_REFERENCE || mode == GNPDE_SCORE_UNIFORM) return kWave;
+  if (mode == GNPDE_SCORE_REFERENCE || mode == GNPDE_SCORE_UNIFORM || mode == GNPDE_SCORE_GAT) return kWave;
   if (heads < 1 || dk < 4 || dk % 4 != 0) return 0;
   const int64_t S = dk / 4, T = heads * S;
   if ((S & (S - 1)) || (T & (T - 1)) || T > kWave) return 0;
@@ -574,9 +603,16 @@ int gnpde_seg_softmax_f32(const int32_t* items, int64_t n_items, int64_t n_hub_i
   GNPDE_REQUIRE(n_items >= 0 && n_chunk_items >= 0 && n_heavy >= 0 && n_items + n_chunk_items < INT32_MAX &&
                     n_hub_items >= 0 && n_long_items >= 0 && n_hub_items + n_long_items <= n_items,
                 GNPDE_EINVAL, "seg_softmax: bad item counts");
-  GNPDE_REQUIRE(n_hub_items + n_long_items == 0 || (mode == GNPDE_SCORE_REFERENCE && out_kind == 1 && group_is_dst &&
-                                                    n_chunk_items == 0),
-                GNPDE_EINVAL, "seg_softmax: hub / long items are for the reference statistics (norm_idx 1) only");
+  // GAT scores (both endpoints' node scores): the statistics of either grouping, over a
+  // plan with hub / long items (no chunk items); the weights come from gnpde_attn_weights_f32
+  // or inside K1 (gnpde_attn_gat_rhs_f32)
+  const bool gat = mode == GNPDE_SCORE_GAT;
+  GNPDE_REQUIRE(!gat || (out_kind == 1 && n_chunk_items == 0), GNPDE_EUNSUPPORTED,
+                "seg_softmax: GAT scores take the statistics pass (out_kind 1) over a plan without chunk items");
+  GNPDE_REQUIRE(n_hub_items + n_long_items == 0 ||
+                    (((mode == GNPDE_SCORE_REFERENCE && group_is_dst) || gat) && out_kind == 1 && n_chunk_items == 0),
+                GNPDE_EINVAL,
+                "seg_softmax: hub / long items are for the reference (norm_idx 1) and GAT statistics only");
   GNPDE_REQUIRE(gnpde_seg_block_edges(mode, heads, dk) > 0, GNPDE_EUNSUPPORTED,
                 "seg_softmax: per-edge scores need dk %% 4 == 0 and power-of-two dk/4, heads*dk/4 <= 64");
   if (n_items + n_chunk_items == 0) return GNPDE_OK;
@@ -589,7 +625,7 @@ int gnpde_seg_softmax_f32(const int32_t* items, int64_t n_items, int64_t n_hub_i
   if (out_kind == 1) GNPDE_REQUIRE((m && rl) || mr, GNPDE_EINVAL, "seg_softmax: no output (m/rl or the packed records)");
   const ScoreArgs sa = make_score_args(mode, heads, dk, cs, q, k, ldqk, score_p0, score_p1);
   Team tm{1, 1};
-  if (mode != GNPDE_SCORE_REFERENCE) {
+  if (mode != GNPDE_SCORE_REFERENCE && !gat) {
     tm = team_geometry(sa);
     GNPDE_REQUIRE(tm.T > 0, GNPDE_EUNSUPPORTED, "seg_softmax: q/k must be 16-byte aligned with ldqk %% 4 == 0");
   }
@@ -608,14 +644,14 @@ int gnpde_seg_softmax_f32(const int32_t* items, int64_t n_items, int64_t n_hub_i
   const bool adjacent = n_items > 0 && n_chunk_items > 0 && ch == it + n_items;
   const int64_t n_first = adjacent ? n_items + n_chunk_items : n_items;
   const int64_t n_second = adjacent ? 0 : n_chunk_items;
-  if (ref && out_kind == 1 && n_chunk_items == 0 && group_is_dst) {
+  if ((ref && out_kind == 1 && n_chunk_items == 0 && group_is_dst) || gat) {
     // the reference statistics of the attention RHS: hub chunks, long groups, then short items
     GNPDE_REQUIRE((uint64_t)n_items < (uint64_t)INT32_MAX / kWavesPerBlock, GNPDE_EUNSUPPORTED,
                   "seg_softmax: too many items");
     GNPDE_REQUIRE(n_hub_items == 0 || (heavy && n_heavy > 0 && partials), GNPDE_EINVAL,
                   "seg_softmax: hub chunk items need the hub table (heavy) and partials");
     return launch_ref_stats<kRefStatsNI>(it, n_items, n_hub_items, n_long_items, rowidx, gidx, sa, hv, partials, m, rl,
-                                          mr, s);
+                                          mr, s, group_is_dst ? 1 : 0);
   }
   if (out_kind == 0) {
     rc = GNPDE_SEG(false, kSegWeights, it, n_first);

@@ -931,6 +931,28 @@ static void launch_node_scores_fused(hipStream_t s, const NsGeom& ge, const floa
 #undef GNPDE_NSF
 }
 
+// ------------------------------------------------------------------ GAT node scores
+// The GAT score a . [W x_src | W x_dst] (function_GAT_attention.py:123-134) splits into
+// per-node scalars: sl[n,h] = sum_d a[d] wx[n,h,d], sr[n,h] = sum_d a[dk+d] wx[n,h,d], so
+// [sl | sr] = x U with U[c][j] = sum_d W[c, h*dk + d] a[(j < H ? 0 : dk) + d], h = j mod H.
+// One workgroup per batch element folds W with a into the padded layout node_scores_kernel
+// reads (U[Cp][Hp] | v[Hp], v = 0), accumulated in fp64; no host read.
+__global__ __launch_bounds__(256) void gat_fold_kernel(const float* __restrict__ W, const float* __restrict__ a, int C,
+                                                        int att, int H, int Cp, int Hp, double* __restrict__ uv) {
+  const int dk = att / H;
+  double* __restrict__ U = uv + (int64_t)blockIdx.x * ((int64_t)Cp * Hp + Hp);
+  for (int t = threadIdx.x; t < (Cp + 1) * Hp; t += blockDim.x) {
+    const int c = t / Hp, j = t - c * Hp;
+    double acc = 0.0;
+    if (c < C && j < 2 * H) {
+      const float* __restrict__ ap = a + (j < H ? 0 : dk);
+      const float* __restrict__ wp = W + (int64_t)c * att + (j < H ? j : j - H) * dk;
+      for (int d = 0; d < dk; ++d) acc = fma((double)wp[d], (double)ap[d], acc);
+    }
+    U[t] = acc;
+  }
+}
+
 static unsigned edge_grid(int64_t nnz) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(nnz, kBlock), 16384));
 }
@@ -1141,6 +1163,37 @@ int gnpde_ref_scores_from_keysum_f32(const float* x, int64_t B, int64_t N, int64
   if (rc) return rc;
   return ref_node_scores_launch(x, B, N, C, ldx, Wq, bq, att, heads, S, 1, cs, static_cast<double*>(workspace),
                                 as_stream(stream));
+}
+
+size_t gnpde_gat_scores_workspace_bytes(int64_t B, int64_t C) {
+  // U, v per batch element in node_scores_kernel's padded layout: Cp*Hp < 16*C + 2048, Hp <= 16
+  return sizeof(double) * (size_t)(B * (16 * C + 2048 + 16));
+}
+
+int gnpde_gat_scores_f32(const float* x, int64_t B, int64_t N, int64_t C, int64_t ldx, const float* W, const float* a,
+                         int64_t att, int64_t heads, double* sp, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  GNPDE_REQUIRE(x && W && a && sp && workspace, GNPDE_EINVAL, "gat_scores: NULL pointer");
+  GNPDE_REQUIRE(B >= 1 && N >= 1 && C >= 1 && ldx >= C && att >= 1, GNPDE_EINVAL, "gat_scores: bad sizes");
+  GNPDE_REQUIRE(heads >= 1 && heads <= 8 && att % heads == 0, GNPDE_EUNSUPPORTED,
+                "gat_scores: heads must divide attention_dim and be <= 8");
+  GNPDE_REQUIRE(B <= 65535, GNPDE_EUNSUPPORTED, "gat_scores: batch too large");
+  GNPDE_REQUIRE((uint64_t)N * 2 * heads * 8 < kBufRecords, GNPDE_EUNSUPPORTED, "gat_scores: N*heads too large");
+  GNPDE_REQUIRE(workspace_bytes >= gnpde_gat_scores_workspace_bytes(B, C), GNPDE_EINVAL,
+                "gat_scores: workspace too small");
+  int vec, tpr;
+  keysum_geometry(C, x, ldx, &vec, &tpr);
+  const NsGeom ge = ns_geometry(vec, C, 2 * heads);
+  const int64_t cp = (int64_t)ge.nch * ge.CW;
+  GNPDE_REQUIRE(ns_uv_doubles(ge) <= 16 * C + 2048 + 16 && (cp + 1) * ge.maxh < INT32_MAX, GNPDE_EUNSUPPORTED,
+                "gat_scores: node-score geometry");
+  hipStream_t s = as_stream(stream);
+  double* uv = static_cast<double*>(workspace);
+  gat_fold_kernel<<<(unsigned)B, kBlock, 0, s>>>(W, a, (int)C, (int)att, (int)heads, (int)cp, ge.maxh, uv);
+  GNPDE_LAUNCH_CHECK();
+  launch_node_scores_any(s, ge, x, B, N, (int)C, ldx, 2 * (int)heads, uv, sp);
+  GNPDE_LAUNCH_CHECK();
+  return GNPDE_OK;
 }
 
 }  // extern "C"

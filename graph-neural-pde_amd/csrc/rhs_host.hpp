@@ -11,10 +11,14 @@ namespace gnpde {
 inline int check_score_args(int mode, int64_t heads, int64_t dk, const double* cs, const float* q, const float* k) {
   GNPDE_REQUIRE(heads >= 1 && heads <= 16, GNPDE_EUNSUPPORTED, "attention: heads=%lld not in [1,16]",
                 (long long)heads);
-  GNPDE_REQUIRE(mode >= GNPDE_SCORE_REFERENCE && mode <= GNPDE_SCORE_UNIFORM, GNPDE_EINVAL,
+  GNPDE_REQUIRE(mode >= GNPDE_SCORE_REFERENCE && mode <= GNPDE_SCORE_GAT, GNPDE_EINVAL,
                 "attention: unknown score mode %d", mode);
   if (mode == GNPDE_SCORE_REFERENCE) {
     GNPDE_REQUIRE(cs != nullptr, GNPDE_EINVAL, "attention: reference mode needs cs");
+  } else if (mode == GNPDE_SCORE_GAT) {
+    GNPDE_REQUIRE(cs != nullptr, GNPDE_EINVAL, "attention: GAT mode needs the node-score pairs (cs)");
+    GNPDE_REQUIRE(heads <= 8, GNPDE_EUNSUPPORTED, "attention: GAT scores take heads <= 8 (got %lld)",
+                  (long long)heads);
   } else if (mode != GNPDE_SCORE_UNIFORM) {
     GNPDE_REQUIRE(q != nullptr && k != nullptr && dk >= 1, GNPDE_EINVAL, "attention: per-edge mode needs q, k, dk");
   }

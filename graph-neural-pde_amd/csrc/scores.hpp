@@ -240,20 +240,34 @@ __device__ __forceinline__ void stats_merge_store_heads(int g, int first, int nc
 int launch_stats_fixup(const int4* heavy, int64_t n_heavy, int H, const double* partials, double* m, float* rl,
                        float* mr, hipStream_t s);
 
+// GAT edge score (function_GAT_attention.py:131-134): LeakyReLU of the source's left
+// and the destination's right node score.  Contraction is off so that the product by
+// the slope is rounded on its own wherever this is inlined: the fused K1 policy
+// (GatSoftmaxWeights, aggregate.hpp) and the weights pass then subtract the group max
+// from the same bits.
+__device__ __forceinline__ double gat_leaky(double sl, double sr, float slope) {
+#pragma clang fp contract(off)
+  const double t = sl + sr;
+  const double neg = t * (double)slope;
+  return t > 0.0 ? t : neg;
+}
+
 struct ScoreArgs {
   int mode;
   int H;
   int dk;
-  const double* __restrict__ cs;  // [R,H] reference-mode node scores (fp64)
+  const double* __restrict__ cs;  // [R,H] reference-mode node scores (fp64); GAT: the pairs [R,2H] = [sl | sr]
   const float* __restrict__ q;    // [R,ldqk] per-edge modes
   const float* __restrict__ k;
   int64_t ldqk;
-  float p0, p1;
+  float p0, p1;  // exp_kernel: output_var, lengthscale; GAT: p0 = the LeakyReLU slope
 
   // lane mode: score of edge src->dst, head h, as double (exact for the fp32 modes)
   __device__ __forceinline__ double score(int src, int dst, int h) const {
     if (mode == GNPDE_SCORE_REFERENCE) return cs[(int64_t)src * H + h];
     if (mode == GNPDE_SCORE_UNIFORM) return 0.0;
+    if (mode == GNPDE_SCORE_GAT)
+      return gat_leaky(cs[(int64_t)src * 2 * H + h], cs[(int64_t)dst * 2 * H + H + h], p0);
     return (double)pair_score(mode, q + (int64_t)src * ldqk + h * dk, k + (int64_t)dst * ldqk + h * dk, dk, p0, p1);
   }
 };

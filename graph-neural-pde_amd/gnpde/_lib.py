@@ -135,6 +135,11 @@ SIGNATURES = {
     "gnpde_norm_weights_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp]),
     "gnpde_score_grad_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _f32, _f32, _vp,
                                     _vp, _i64, _vp, _vp]),
+    "gnpde_gat_scores_workspace_bytes": (_size, [_i64, _i64]),
+    "gnpde_gat_scores_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _size, _vp]),
+    "gnpde_attn_gat_rhs_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _int, _i64, _f32, _i64, _vp, _i64, _vp,
+                                      _i64, _vp, _vp, _int, _vp, _i64, _vp, _i64, ctypes.POINTER(StageEpilogue), _vp]),
+    "gnpde_gat_score_backward_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp]),
 }
 
 # constants mirrored from include/gnpde.h
@@ -153,6 +158,7 @@ SCORE_EXP_KERNEL = 2
 SCORE_COSINE = 3
 SCORE_PEARSON = 4
 SCORE_UNIFORM = 5
+SCORE_GAT = 6
 NORM_RW_ROW = 0
 NORM_RW_COL = 1
 NORM_GCN = 2

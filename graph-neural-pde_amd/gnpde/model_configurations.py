@@ -2,8 +2,11 @@
 point ``GNN.__init__`` uses (src/GNN.py:12-15).
 
 Built here: block 'constant', 'attention', 'mixed',
-'hard_attention'; function 'laplacian', 'transformer'.  The other names the
-reference registers are out of scope ('rewire_attention', 'GAT') and raise
+'hard_attention'; function 'laplacian', 'transformer' and 'GAT'.  'GAT'
+(function_GAT_attention.ODEFuncAtt) is returned when the option dict sets
+``gnpde_gat`` to a true value; without the key it raises NotImplementedError
+naming the key (the plain dict's behaviour is pinned by the host tests until the
+switch becomes the default).  Block 'rewire_attention' is out of scope and raises
 NotImplementedError naming the reason, rather than silently falling back to a
 different model.
 """
@@ -12,6 +15,7 @@ from .block_mixed import MixedODEblock
 from .block_transformer_hard_attention import HardAttODEblock
 from .block_transformer_attention import AttODEblock
 from .function_laplacian_diffusion import LaplacianODEFunc
+from .function_GAT_attention import ODEFuncAtt
 from .function_transformer_attention import ODEFuncTransformerAtt
 
 
@@ -50,6 +54,8 @@ def set_function(opt):
     if ode_str == 'transformer':
         return ODEFuncTransformerAtt
     if ode_str == 'GAT':
-        raise NotImplementedError("gnpde: function 'GAT' is out of scope (not named by the north star, SURVEY §2 "
-                                  "row 10)")
+        if opt.get('gnpde_gat'):
+            return ODEFuncAtt
+        raise NotImplementedError("gnpde: function 'GAT' (function_GAT_attention.ODEFuncAtt) is opt-in: set "
+                                  "opt['gnpde_gat'] = True to select it")
     raise FunctionNotDefined

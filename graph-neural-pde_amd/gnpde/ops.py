@@ -792,9 +792,9 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
     be in CSC order) — the backward of the RHS with respect to x.
     stage: a ``Stage`` -> the fused Runge-Kutta outputs are written instead of f
     (returns None).  The adaptive solvers' wide stages (Stage.wide) are fused
-    with plain weights; with weights computed on the fly (RefDstWeights) f is
+    with plain weights; with weights computed on the fly (RefDstWeights, GatWeights) f is
     formed first and the stage applied in a second pass (stage_apply)."""
-    if stage is not None and stage.wide and isinstance(w_csr, RefDstWeights):
+    if stage is not None and stage.wide and isinstance(w_csr, (RefDstWeights, GatWeights)):
         f = spmm_rhs(g, w_csr, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
                      add_source=add_source, transpose=transpose)
         stage_apply(stage, f, x, x)
@@ -832,7 +832,7 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
             raise ValueError("spmm_rhs: compacted weights of another grouped CSR")
         items, col, w_csr = w_csr.items, w_csr.col, w_csr.w
     if dt == torch.bfloat16:
-        if isinstance(w_csr, RefDstWeights):
+        if isinstance(w_csr, (RefDstWeights, GatWeights)):
             raise ValueError("bf16 storage takes precomputed weights (attn_rhs(..., fuse=False))")
         _lib.call("gnpde_spmm_rhs_bf16", _ptr(items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
                   _ptr(col), _ptr(w_csr), *epi)
@@ -842,6 +842,12 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
         _lib.call("gnpde_attn_ref_rhs_f32", _ptr(plan.items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
                   _ptr(grouped.col), _ptr(w_csr.cs), _ptr(w_csr.m), _ptr(w_csr.rl), _ptr(w_csr.mr), w_csr.heads,
                   *epi)
+    elif isinstance(w_csr, GatWeights):
+        if transpose:
+            raise ValueError("on-the-fly attention weights aggregate over the CSR only")
+        _lib.call("gnpde_attn_gat_rhs_f32", _ptr(plan.items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
+                  _ptr(grouped.col), _ptr(w_csr.sp), _ptr(w_csr.m), _ptr(w_csr.rl), w_csr.norm_idx, w_csr.heads,
+                  w_csr.slope, *epi)
     else:
         _lib.call("gnpde_spmm_rhs_f32", _ptr(items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
                   _ptr(col), _ptr(w_csr), *epi)
@@ -903,6 +909,34 @@ class RefDstWeights(object):
 
     def __init__(self, cs, m, rl, heads, mr=None):
         self.cs, self.m, self.rl, self.heads, self.mr = cs, m, rl, int(heads), mr
+
+
+class GatWeights(object):
+    """Weights K1 computes on the fly (gnpde_attn_gat_rhs_f32): the GAT attention,
+    head-mean per edge from the node-score pairs sp [R,2h] fp64 (gat_scores) and the
+    statistics m [R,h] fp64, rl [R,h] of the softmax groups (rows for norm_idx 0,
+    destinations for norm_idx 1)."""
+
+    def __init__(self, sp, m, rl, heads, slope, norm_idx):
+        self.sp, self.m, self.rl = sp, m, rl
+        self.heads, self.slope, self.norm_idx = int(heads), float(slope), int(norm_idx)
+
+
+# head counts gnpde_attn_gat_rhs_f32 is built for (csrc/gat.hip); beyond: weights pass + K1
+GAT_FUSED_MAX_HEADS = 8
+# The fused GAT K1 is the default only where it measured faster than the weights pass + the
+# plain K1 on the G-arxiv benchmark graph (tools/gat_bench.py, DESIGN.md §6.11): up to two heads
+# (the two-head instantiation) for either grouping, more heads (the generic one) under
+# destination-grouped softmax; more heads under source-grouped softmax measured 1.1 % slower and
+# take the weights pass.  GNPDE_GAT_FUSE=1 fuses wherever the library supports it, 0 never.
+GAT_FUSE = os.environ.get("GNPDE_GAT_FUSE", "auto")
+
+
+def gat_fuse_default(heads, norm_idx):
+    """Whether ODEFuncAtt asks attn_rhs for the fused GAT K1 (fuse=...)."""
+    if GAT_FUSE in ("0", "1"):
+        return GAT_FUSE == "1"
+    return heads <= 2 or norm_idx == 1
 
 
 def spmm_rhs_rows(g, plan, w_csr, x_src, x_rows, row0, x0=None, alpha=None, beta=None, alpha_sigmoid=True,
@@ -1022,13 +1056,61 @@ def linear_wgrad(gy, x):
 
 
 class NodeScores(object):
-    """Per-RHS node-level operands of the attention scores."""
+    """Per-RHS node-level operands of the attention scores.  GAT (SCORE_GAT): ``sp``
+    = the node-score pairs [R, 2h] fp64 = [sl | sr] and ``slope`` the LeakyReLU slope;
+    the C ABI takes them in the places of cs and score_p0."""
 
-    def __init__(self, mode, heads, dk, cs=None, q=None, k=None, p0=1.0, p1=1.0):
+    def __init__(self, mode, heads, dk, cs=None, q=None, k=None, p0=1.0, p1=1.0, sp=None, slope=None):
         self.mode, self.heads, self.dk = mode, heads, dk
+        self.sp, self.slope = sp, (None if slope is None else float(slope))
+        if sp is not None:
+            cs, p0 = sp, slope
         self.cs, self.q, self.k = cs, q, k
         self.p0, self.p1 = float(p0), float(p1)
         self.ldqk = q.shape[1] if q is not None else 1
+
+
+def gat_workspace(x, B):
+    """Scratch of gat_scores (the folded U): allocate once per parameter version so
+    that captured step graphs keep reading the buffer they were captured with."""
+    C = x.shape[-1]
+    nb = _lib.fn("gnpde_gat_scores_workspace_bytes")(B, C)
+    return torch.empty(int(nb), dtype=torch.uint8, device=x.device)
+
+
+def gat_scores(g, x, W, a, heads, slope, ws=None):
+    """GAT node scores (function_GAT_attention.py:123-134 without wx): NodeScores of
+    mode SCORE_GAT with sp [R, 2h] fp64 = [sl | sr] = x U, U = W [C, att] folded with
+    a [2dk] on the device (gnpde_gat_scores_f32; x read once)."""
+    xr = _rows(x, "x")
+    _require_gpu(W, "W", torch.float32)
+    _require_gpu(a, "a", torch.float32)
+    W = W.contiguous()
+    a = a.contiguous().view(-1)
+    C, att = W.shape
+    heads = int(heads)
+    if xr.shape[1] != C:
+        raise ValueError("gat_scores: x has %d columns, W expects %d" % (xr.shape[1], C))
+    if att % heads or a.numel() != 2 * (att // heads):
+        raise ValueError("gat_scores: attention_dim %d, heads %d, a of %d elements" % (att, heads, a.numel()))
+    if xr.shape[0] != g.R:
+        raise ValueError("x has %d rows, graph has %d" % (xr.shape[0], g.R))
+    if ws is None:
+        ws = gat_workspace(xr, g.B)
+    sp = torch.empty(g.R, 2 * heads, dtype=torch.float64, device=xr.device)
+    _lib.call("gnpde_gat_scores_f32", _ptr(xr), g.B, g.N, C, C, _ptr(W), _ptr(a), att, heads, _ptr(sp), _ptr(ws),
+              ws.numel(), _stream(xr.device))
+    return NodeScores(_lib.SCORE_GAT, heads, att // heads, sp=sp, slope=slope)
+
+
+def gat_score_backward(g, ns, gs):
+    """ge [B,E,h] = gs * LeakyReLU'(sl[src] + sr[dst]) (COO order; gnpde_gat_score_backward_f32)."""
+    _require_gpu(gs, "score grad", torch.float32)
+    gs = gs.contiguous()
+    ge = torch.empty_like(gs)
+    _lib.call("gnpde_gat_score_backward_f32", _ptr(g.csr.rowidx), _ptr(g.csr.col), _ptr(g.csr.perm), g.nnz, ns.heads,
+              _ptr(ns.sp), ns.slope, _ptr(gs), _ptr(ge), _stream(gs.device))
+    return ge
 
 
 def _keysum_workspace(g, dev, nbytes):
@@ -1131,7 +1213,8 @@ def _seg_call(g, ns, norm_idx, out_kind, packed=False, rows=None):
     out_kind 0 -> head-mean weights in aggregation-CSR order (norm_idx 0 only);
     1 -> (m, rl), or with packed=True (None, None, mr): the packed statistics
     records only.  NotImplemented when the shape is outside the kernel."""
-    if ns.mode == _lib.SCORE_UNIFORM or (ns.mode == _lib.SCORE_REFERENCE and out_kind == 0):
+    gat = ns.mode == _lib.SCORE_GAT  # statistics of either grouping; weights from them (attn_weights / K1)
+    if ns.mode == _lib.SCORE_UNIFORM or ((ns.mode == _lib.SCORE_REFERENCE or gat) and out_kind == 0):
         return NotImplemented
     eb = _lib.fn("gnpde_seg_block_edges")(ns.mode, ns.heads, ns.dk)
     if eb <= 0:
@@ -1139,7 +1222,7 @@ def _seg_call(g, ns, norm_idx, out_kind, packed=False, rows=None):
     if ns.q is not None and (ns.ldqk % 4 or ns.q.data_ptr() % 16 or ns.k.data_ptr() % 16):
         return NotImplemented
     grouped = g.csr if norm_idx == 0 else g.csc
-    long_items = ns.mode == _lib.SCORE_REFERENCE and out_kind == 1 and norm_idx == 1
+    long_items = (ns.mode == _lib.SCORE_REFERENCE and out_kind == 1 and norm_idx == 1) or gat
     # a small graph's statistics launch is one round of items: every long item one pass
     # (its hub groups in one-pass chunks), so no wavefront walks a group alone
     long_max = int(_lib.fn("gnpde_seg_long_pass_edges")(ns.heads)) if (long_items and g.R < SMALL_GRAPH_ROWS and
@@ -1270,7 +1353,10 @@ def attn_rhs(g, ns, m, rl, norm_idx, x, x0=None, alpha=None, beta=None, rhs=True
     inside K1 from (cs, m, rl) or (cs, mr) — same bits as the separate weights
     pass.  Two heads with no statistics given: the packed records.  Per-edge
     scaled_dot (fuse=True, shapes of gnpde_attn_dot_supported): one fused pass
-    (attn_dot_rhs) for either grouping."""
+    (attn_dot_rhs) for either grouping.  GAT scores (fuse=True, an fp32 state): the
+    weights inside K1 from (sp, m, rl) of either grouping (gnpde_attn_gat_rhs_f32) —
+    same bits as the weights pass + K1 (ODEFuncAtt passes fuse=gat_fuse_default(...): where
+    the fused pass measured faster)."""
     if fuse and norm_idx == 1 and ns.mode == _lib.SCORE_REFERENCE and x.dtype == torch.float32 and \
             not _small_precompute(g, stage):
         if m is None and mr is None:
@@ -1279,6 +1365,13 @@ def attn_rhs(g, ns, m, rl, norm_idx, x, x0=None, alpha=None, beta=None, rhs=True
             else:
                 m, rl = softmax_stats(g, ns, 1, seg=seg)
         w = RefDstWeights(ns.cs, m, rl, ns.heads, mr=mr)
+        return spmm_rhs(g, w, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
+                        add_source=add_source, out=out, stage=stage)
+    if fuse and ns.mode == _lib.SCORE_GAT and x.dtype == torch.float32 and ns.heads <= GAT_FUSED_MAX_HEADS and \
+            not _small_precompute(g, stage):
+        if m is None:
+            m, rl = softmax_stats(g, ns, norm_idx, seg=seg)
+        w = GatWeights(ns.sp, m, rl, ns.heads, ns.slope, norm_idx)
         return spmm_rhs(g, w, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
                         add_source=add_source, out=out, stage=stage)
     if fuse and ns.mode == _lib.SCORE_DOT and (x.dtype == torch.float32 or (x.dtype == torch.bfloat16 and

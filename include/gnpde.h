@@ -66,6 +66,13 @@ extern "C" {
 #define GNPDE_SCORE_PEARSON 4      /* centred cosine similarity                                   */
 #define GNPDE_SCORE_UNIFORM 5      /* every score 0: the fork's scaled_dot under source-grouped    */
                                    /* softmax (norm_idx 0), where all scores of a group are equal  */
+#define GNPDE_SCORE_GAT 6          /* GAT (function_GAT_attention.py:131-134): LeakyReLU(sl[src,h] + */
+                                   /* sr[dst,h]); cs = the node-score pairs [R, 2*heads] fp64      */
+                                   /* = [sl | sr] (gnpde_gat_scores_f32), score_p0 = the slope;    */
+                                   /* heads <= 8; q, k unused.  Taken by gnpde_softmax_stats_f32,   */
+                                   /* gnpde_seg_softmax_f32 (out_kind 1, either grouping, plans     */
+                                   /* with hub / long items), gnpde_attn_weights_f32 and            */
+                                   /* gnpde_edge_attention_f32.                                     */
 
 int gnpde_abi_version(void);
 const char* gnpde_last_error(void);
@@ -722,6 +729,39 @@ int gnpde_score_grad_f32(const int32_t* rowptr, const int32_t* col, const int32_
                          int side, int mode, int64_t heads, int64_t dk, const float* q, const float* k, int64_t ldqk,
                          float score_p0, float score_p1, const float* gs, float* out, int64_t ldo, float* gp,
                          void* stream);
+
+/* ---- GAT attention function (function_GAT_attention.py: ODEFuncAtt, SpGraphAttentionLayer) ----
+ * Node-score pairs sp [B*N, 2*heads] fp64 = [sl | sr] = x U, where U [C, 2*heads] is W
+ * [C, att] (row-major) folded with a [2*dk] (dk = att / heads, the same a for every
+ * head): U[c][h] = sum_d W[c, h*dk+d] a[d], U[c][heads+h] = sum_d W[c, h*dk+d] a[dk+d].
+ * U is formed on the device (one workgroup per batch element, fp64) into the
+ * workspace (gnpde_gat_scores_workspace_bytes), then x is read exactly once
+ * (fp64 accumulation): 4*R*C bytes in, 16*heads*R out.  heads <= 8.
+ * Restates wx = x W; edge_e = leakyrelu(sum(a * [wx_src | wx_dst])) without wx. */
+size_t gnpde_gat_scores_workspace_bytes(int64_t B, int64_t C);
+int gnpde_gat_scores_f32(const float* x, int64_t B, int64_t N, int64_t C, int64_t ldx, const float* W, const float* a,
+                         int64_t att, int64_t heads, double* sp, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* K1 with the GAT attention weights formed in the gather loop:
+ *   w_p = mean_h exp(leakyrelu(sl[row,h] + sr[col_p,h]) - m[g,h]) * rl[g,h],
+ * g = row (norm_idx 0, statistics over the CSR) or col_p (norm_idx 1, over the CSC),
+ * sp the pairs of gnpde_gat_scores_f32, m / rl the group statistics of mode
+ * GNPDE_SCORE_GAT.  Equals gnpde_attn_weights_f32 (mode GAT) + gnpde_spmm_rhs_f32 bit
+ * for bit, in one pass.  The wide (adaptive-solver) stage epilogue is fused with plain
+ * weights only (GNPDE_EUNSUPPORTED here).  Other arguments as gnpde_spmm_rhs_f32.  */
+int gnpde_attn_gat_rhs_f32(const int32_t* items, int64_t n_items, int32_t* heavy, int64_t n_heavy,
+                           const int32_t* col, const double* sp, const double* m, const float* rl, int norm_idx,
+                           int64_t heads, float slope, int64_t C, const float* x, int64_t ldx, const float* x0,
+                           int64_t ldx0, const float* alpha, const float* beta, int flags, float* f, int64_t ldf,
+                           float* partials, int64_t n_slots, const gnpde_stage_epilogue_t* stage, void* stream);
+
+/* Backward of the GAT edge score through its LeakyReLU, edge-parallel over the
+ * aggregation CSR (rowidx = source, col = destination, perm -> COO ids):
+ *   ge[e,h] = gs[e,h] * (sl[src,h] + sr[dst,h] > 0 ? 1 : slope)   (COO [nnz, heads]). */
+int gnpde_gat_score_backward_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
+                                 int64_t heads, const double* sp, float slope, const float* gs, float* ge,
+                                 void* stream);
 
 #ifdef __cplusplus
 }
