@@ -160,6 +160,48 @@ struct GatSoftmaxWeights {
   }
 };
 
+// Reference-mode (fork scaled_dot) attention under destination-grouped SQUAREPLUS
+// normalisation (square_plus, src/utils.py:129-140), head mean taken on the fly.  The
+// squareplus value of an edge is a per-node quantity of its source, p[row, h] =
+// squareplus_p(cs[row, h] - M_b) (gnpde_squareplus_stats_f32 forms the [R, H] array once per
+// RHS), and the group statistics rl[c, h] = 1 / (sum p + 1e-16) belong to its destination c:
+//   w = (1/H) sum_h p[row, h] * rl[c, h]
+// — no transcendental per edge.  load() issues the rl[c, :] gather with the column index;
+// p[row, :] is one address per row slot (loop-invariant: read once per item).  Same
+// arithmetic, in the same order, as squareplus_edge_kernel (squareplus.hip), so the fused
+// launch equals gnpde_squareplus_weights_f32 + gnpde_spmm_rhs_f32 bit for bit.
+// MAXH > 0: heads <= MAXH, rl loaded up front; MAXH == 0: any heads <= 16, loaded in finish().
+template <int MAXH>
+struct RefDstSquareplusWeights {
+  const float* __restrict__ pn;
+  const float* __restrict__ rl;
+  int H;
+  struct Raw {
+    float rr[MAXH > 0 ? MAXH : 1];
+    int c;
+  };
+  __device__ __forceinline__ Raw load(int /*row*/, int /*p*/, int c) const {
+    Raw r;
+    r.c = c;
+    if constexpr (MAXH > 0) {
+#pragma unroll
+      for (int h = 0; h < MAXH; ++h) r.rr[h] = rl[(int64_t)c * H + (h < H ? h : 0)];
+    }
+    return r;
+  }
+  __device__ __forceinline__ float finish(int row, const Raw& r) const {
+    float acc = 0.f;
+    if constexpr (MAXH > 0) {
+#pragma unroll
+      for (int h = 0; h < MAXH; ++h)
+        if (h < H) acc = squareplus_mean_step(pn[(int64_t)row * H + h], r.rr[h], acc);
+    } else {
+      for (int h = 0; h < H; ++h) acc = squareplus_mean_step(pn[(int64_t)row * H + h], rl[(int64_t)r.c * H + h], acc);
+    }
+    return acc / (float)H;
+  }
+};
+
 // Policies that take the narrow-row lane geometries of launch_agg_vec (several rows per
 // wavefront below 17 lanes): the plain weights, and the GAT policy, which promises the
 // bits of the weights pass + the plain K1 at every width, so it sums in the same order.
@@ -167,6 +209,8 @@ template <class WP>
 struct takes_narrow_rows : std::is_same<WP, PlainWeights> {};
 template <int MAXH, bool DST>
 struct takes_narrow_rows<GatSoftmaxWeights<MAXH, DST>> : std::true_type {};
+template <int MAXH>
+struct takes_narrow_rows<RefDstSquareplusWeights<MAXH>> : std::true_type {};  // the same promise
 
 template <class WP>
 __host__ __device__ inline PlainWeights as_plain(const WP& wp) {

@@ -252,6 +252,21 @@ __device__ __forceinline__ double gat_leaky(double sl, double sr, float slope) {
   return t > 0.0 ? t : neg;
 }
 
+// squareplus of a shifted score t = s - max(s) <= 0 (src/utils.py:133: (t + sqrt(t^2 + 4)) / 2)
+// in the algebraically equal form 2 / (sqrt(t^2 + 4) - t): both terms of the denominator are
+// positive, so nothing cancels (the reference form loses ~1 % in fp32 at t = -1000).
+// Result in (0, 1].  Contraction off: the weights pass, the statistics and the fused K1
+// policy (RefDstSquareplusWeights, aggregate.hpp) round the same way wherever this is inlined.
+__device__ __forceinline__ float squareplus_p(float t) {
+#pragma clang fp contract(off)
+  const float tt = t * t;
+  return 2.0f / (sqrtf(tt + 4.0f) - t);
+}
+
+// Head mean of p[h] * rl[h] as the squareplus weights pass and the fused policy form it:
+// fmaf in head order, then one division.
+__device__ __forceinline__ float squareplus_mean_step(float p, float rl, float acc) { return fmaf(p, rl, acc); }
+
 struct ScoreArgs {
   int mode;
   int H;

@@ -140,6 +140,20 @@ SIGNATURES = {
     "gnpde_attn_gat_rhs_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _int, _i64, _f32, _i64, _vp, _i64, _vp,
                                       _i64, _vp, _vp, _int, _vp, _i64, _vp, _i64, ctypes.POINTER(StageEpilogue), _vp]),
     "gnpde_gat_score_backward_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp]),
+    "gnpde_score_max_workspace_bytes": (_size, [_i64]),
+    "gnpde_score_max_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _i64, _i64, _vp, _vp, _vp, _i64, _f32,
+                                   _f32, _vp, _vp, _vp, _vp, _size, _vp]),
+    "gnpde_squareplus_stats_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _i64, _i64, _int, _i64, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp]),
+    "gnpde_squareplus_weights_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp,
+                                            _vp]),
+    "gnpde_squareplus_attention_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp,
+                                              _vp]),
+    "gnpde_attn_sp_rhs_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                     _int, _vp, _i64, _vp, _i64, ctypes.POINTER(StageEpilogue), _vp]),
+    "gnpde_squareplus_backward_workspace_bytes": (_size, [_i64]),
+    "gnpde_squareplus_backward_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _size,
+                                             _vp]),
 }
 
 # constants mirrored from include/gnpde.h

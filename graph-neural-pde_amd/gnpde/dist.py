@@ -498,6 +498,16 @@ class _Comm(object):
         dist.all_gather_into_tensor(out, t, group=self.group)
 
 
+def _refuse_square_plus(square_plus, who):
+    """The sharded attention classes normalise with the edge softmax only: the squareplus
+    shift is a maximum over ALL edges of a batch element (one more collective in front of
+    the statistics), which the sharded passes do not form."""
+    if square_plus:
+        raise NotImplementedError("%s: square_plus (the squareplus attention normalisation) is not sharded; "
+                                  "run it on one GPU (gnpde.ODEFuncTransformerAtt with "
+                                  "opt['gnpde_square_plus'])" % who)
+
+
 class _HipAttentionLocal(object):
     """A rank's arithmetic of the sharded transformer RHS on the HIP path (tests
     inject a CPU object with the same methods to run the collectives under gloo)."""
@@ -667,7 +677,8 @@ class ColumnShardedTransformer(object):
 
     def __init__(self, edge_index, num_nodes, C, Wq, bq, Wk, bk, heads, norm_idx, alpha, score_mode='reference',
                  beta=None, x0_local=None, add_source=False, alpha_sigmoid=True, group=None, local=None,
-                 chunk=None, comm=None, partition_stats=True, edge_weights=None):
+                 chunk=None, comm=None, partition_stats=True, edge_weights=None, square_plus=False):
+        _refuse_square_plus(square_plus, "ColumnShardedTransformer")
         self.group = group
         self.comm = comm if comm is not None else _Comm(group)
         self.rank = dist.get_rank(group)
@@ -936,7 +947,8 @@ class RowShardedTransformer(object):
 
     def __init__(self, edge_index, num_nodes, C, Wq, bq, Wk, bk, heads, norm_idx, alpha, score_mode='reference',
                  beta=None, x0_local=None, add_source=False, alpha_sigmoid=True, group=None,
-                 chunk=None, row_weight=ROW_WEIGHT, comm=None, local=None, partition_stats=True):
+                 chunk=None, row_weight=ROW_WEIGHT, comm=None, local=None, partition_stats=True, square_plus=False):
+        _refuse_square_plus(square_plus, "RowShardedTransformer")
         if edge_index.shape[0] != 1:
             raise NotImplementedError("RowShardedTransformer: one graph (B = 1); shard batches with shard_batch")
         if int(norm_idx) not in (0, 1) or score_mode not in ('reference', 'per_edge'):

@@ -23,11 +23,23 @@ head-mean attention into [B,N,N] for a dense matmul.  Here one RHS is:
    and norm_idx 0 every score of a source group is equal, so the weights are
    1/outdeg for any x: computed once per graph.
 
+``square_plus`` (with the opt-in key ``gnpde_square_plus``; the reference's call at
+:264 passes a 2-D slice and omits num_nodes) normalises the scores with
+``utils.squareplus(prods, edge[:, norm_idx, :], None)`` instead of the softmax:
+steps 2-3 become the global score maximum per batch element (gnpde_score_max_f32;
+per-edge modes store their scores once), the group sums of p = squareplus(s - M_b)
+(gnpde_squareplus_stats_f32; for the fork's scores p is per node) and the
+head-mean weights — inside K1 for the fork's scores under norm_idx 1
+(gnpde_attn_sp_rhs_f32: no transcendental per edge), else a weights pass
+(gnpde_squareplus_weights_f32) + K1.  M, p and the stored scores live in buffers
+cached on the layer (``squareplus_buffers``); nothing is read on the host.  The
+uniform case keeps its cached 1/outdeg weights.  DESIGN.md §6.12.
+
 V and Wout are dead when ``mix_features=False`` (:33-41) and are never
 computed; the parameters exist for state_dict compatibility.  Settings the
-fork cannot execute (``mix_features`` :23-31, ``square_plus`` :264,
-``multi_modal`` :171/222, beltrami+exp_kernel :164-167) raise
-NotImplementedError.  ``reweight_attention`` is a no-op in the fork (the
+fork cannot execute (``mix_features`` :23-31, ``square_plus`` :264 without
+``gnpde_square_plus``, ``multi_modal`` :171/222, beltrami+exp_kernel :164-167)
+raise NotImplementedError.  ``reweight_attention`` is a no-op in the fork (the
 layer's ``edge_weights`` is captured as None at construction, :15 / :261) and
 is a no-op here.
 
@@ -43,8 +55,12 @@ transformer ODEFunc then composes it with the Laplacian RHS autograd
 SDDMM.  exp_kernel / cosine_sim / pearson: one pass per side over the grouped
 CSR / CSC turns dL/ds into dL/dq and dL/dk (gnpde_score_grad_f32, exp_kernel
 also into dL/d output_var and dL/d lengthscale), then the same projection
-backward.  Every gradient is pinned by fixtures of the reference's own fp64
-autograd (tests/golden/grad_*.npz, tests/test_gpu_grad_golden.py).
+backward.  Under squareplus the first pass is gnpde_squareplus_backward_f32 (the
+group term and the derivative of the global maximum, which lands on the arg-max
+position found in the forward); the score chain rules take its result unchanged.
+Every gradient is pinned by fixtures of the reference's own fp64 autograd
+(tests/golden/grad_*.npz, tests/test_gpu_grad_golden.py; squareplus:
+tests/golden/squareplus/spgrad_*.npz, tests/test_gpu_squareplus.py).
 """
 import torch
 from torch import nn
@@ -58,9 +74,10 @@ def _check_supported(opt):
     if opt.get('mix_features', False):
         raise NotImplementedError("gnpde: mix_features=True is broken in the reference "
                                   "(function_transformer_attention.py:29-31 uses a tuple as a tensor)")
-    if opt.get('square_plus', False):
+    if opt.get('square_plus', False) and not opt.get('gnpde_square_plus', False):
         raise NotImplementedError("gnpde: square_plus is broken in the reference (utils.squareplus called "
-                                  "without num_nodes, :264) and not implemented")
+                                  "with a 2-D slice and without num_nodes, :264); set opt['gnpde_square_plus'] = "
+                                  "True to run the intended call, utils.squareplus(prods, edge[:, norm_idx, :], None)")
     if opt.get('multi_modal', False):
         raise NotImplementedError("gnpde: multi_modal is broken in the reference and out of scope")
     if opt.get('beltrami', False) and opt.get('attention_type', 'scaled_dot') == 'exp_kernel':
@@ -79,10 +96,12 @@ class _EdgeAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Wq, bq, Wk, bk, ov, ls, layer, g, norm_idx):
-        ns, m, rl = layer.scores_and_stats(g, x.detach(), norm_idx)
-        att = ops.edge_attention(g, ns, m, rl, norm_idx)
+        ns, m, rl = layer.scores_and_stats(g, x.detach(), norm_idx, fresh=True)
+        att = layer.edge_attention(g, ns, m, rl, norm_idx)
         ctx.save_for_backward(x, Wq, bq, Wk, bk, att)
         ctx.layer, ctx.g, ctx.norm_idx, ctx.ns = layer, g, norm_idx, ns
+        # squareplus (m is then the SquareplusState): its backward reads rl and the arg-max positions
+        ctx.sp = (rl, m.amax) if isinstance(m, ops.SquareplusState) else None
         ctx.p_shapes = (None if ov is None else (ov.shape, ov.dtype), None if ls is None else (ls.shape, ls.dtype))
         return att
 
@@ -91,7 +110,11 @@ class _EdgeAttention(torch.autograd.Function):
         x, Wq, bq, Wk, bk, att = ctx.saved_tensors
         g, ns, norm_idx = ctx.g, ctx.ns, ctx.norm_idx
         grouped = g.csr if norm_idx == 0 else g.csc
-        gs = ops.softmax_backward(grouped, att, g_att.float())
+        if ctx.sp is not None:
+            # squareplus is not shift-invariant: dL/ds carries the term of the global maximum
+            gs = ops.squareplus_backward(grouped, att, g_att.float(), *ctx.sp)
+        else:
+            gs = ops.softmax_backward(grouped, att, g_att.float())
         g_ov = g_ls = None
         if ns.mode == ops._lib.SCORE_UNIFORM:
             # every score of a softmax group is the same node score: the attention does not move
@@ -221,6 +244,7 @@ class SpGraphTransAttentionLayer(nn.Module):
         self._graph_key = None
         self._uniform = None  # (graph, NodeScores, m, rl, csr weights) for the uniform fast path
         self._wcat = None     # (param versions, ([Wq;Wk], [bq;bk]))
+        self._sp_bufs = None  # (state shape, ops.SquareplusState): the squareplus operands
 
     def init_weights(self, m):
         """Constant 1e-5 init (:153-157)."""
@@ -250,8 +274,27 @@ class SpGraphTransAttentionLayer(nn.Module):
         return (self.score_mode == 'reference' and norm_idx == 0 and
                 self.opt.get('attention_type', 'scaled_dot') == 'scaled_dot')
 
-    def scores_and_stats(self, g, x, norm_idx):
-        """(NodeScores, m, rl) for this RHS evaluation."""
+    @property
+    def square_plus(self):
+        """opt['square_plus'] (accepted with opt['gnpde_square_plus'], _check_supported)."""
+        return bool(self.opt.get('square_plus', False))
+
+    def squareplus_buffers(self, g, x):
+        """The squareplus operands (ops.SquareplusState: M, the per-node p or the stored
+        scores, the reduction scratch) cached per state shape and device — stable buffers,
+        so captured step graphs keep replaying and the RHS reads nothing on the host."""
+        mode = ops.SCORE_MODES[(self.opt.get('attention_type', 'scaled_dot'), self.score_mode)]
+        key = (g.B, g.N, g.E, self.h, mode, str(x.device))
+        if self._sp_bufs is None or self._sp_bufs[0] != key:
+            self._sp_bufs = (key, ops.squareplus_buffers(g, mode, self.h, x.device))
+        return self._sp_bufs[1]
+
+    def scores_and_stats(self, g, x, norm_idx, fresh=False):
+        """(NodeScores, m, rl) for this RHS evaluation; under squareplus m is the
+        ops.SquareplusState (the global maxima M and what the later passes read) — in the
+        layer's cached buffers, or new ones with fresh=True (autograd keeps them).
+        Uniform scores keep the cached 1/outdeg statistics under either normaliser:
+        att = p / (d p + 1e-16) is 1/outdeg to within 1e-16 / (d p)."""
         if self.is_uniform(norm_idx):
             if self._uniform is None or self._uniform[0] is not g:
                 ns = ops.uniform_scores(self.h)
@@ -259,8 +302,17 @@ class SpGraphTransAttentionLayer(nn.Module):
                 self._uniform = (g, ns, m, rl, ops.attn_weights(g, ns, m, rl, 0))
             return self._uniform[1:4]
         ns = self.node_scores(g, x)
+        if self.square_plus:
+            sq = ops.score_max(g, ns, None if fresh else self.squareplus_buffers(g, x))
+            return ns, sq, ops.squareplus_stats(g, ns, sq, norm_idx)
         m, rl = ops.softmax_stats(g, ns, norm_idx)
         return ns, m, rl
+
+    def edge_attention(self, g, ns, m, rl, norm_idx):
+        """attention [B,E,h] (COO) from scores_and_stats' result, under the layer's normaliser."""
+        if isinstance(m, ops.SquareplusState):
+            return ops.squareplus_attention(g, ns, m, rl, norm_idx)
+        return ops.edge_attention(g, ns, m, rl, norm_idx)
 
     def uniform_weights(self, g):
         self.scores_and_stats(g, None, 0)
@@ -298,7 +350,7 @@ class SpGraphTransAttentionLayer(nn.Module):
                                        norm_idx)
             return att, (None, None)
         ns, m, rl = self.scores_and_stats(g, x, norm_idx)
-        return ops.edge_attention(g, ns, m, rl, norm_idx), (None, None)
+        return self.edge_attention(g, ns, m, rl, norm_idx), (None, None)
 
     def __repr__(self):
         return self.__class__.__name__ + ' (' + str(self.in_features) + ' -> ' + str(self.out_features) + ')'
@@ -341,6 +393,10 @@ class ODEFuncTransformerAtt(ODEFunc):
             st.append(lay._uniform)
         elif lay.uses_wcat():
             st.append(lay.wcat())
+        if lay.square_plus and not lay.is_uniform(int(self.opt['attention_norm_idx'])):
+            # the squareplus operands (M, p / stored scores) and the statistics plan of the groups
+            grouped = g.csr if int(self.opt['attention_norm_idx']) == 0 else g.csc
+            st.extend([lay.squareplus_buffers(g, x), grouped.stats_plan, g.csr.rowidx])
         if self.opt.get('add_source', False):
             st.append(self.stable_x0(x))
         return st
@@ -395,6 +451,13 @@ class ODEFuncTransformerAtt(ODEFunc):
                   stage=stage)
         if lay.is_uniform(norm_idx):
             return ops.spmm_rhs(g, lay.uniform_weights(g), x, **kw)
+        if lay.square_plus:
+            # squareplus: score maximum, group statistics, then the fused K1 (reference scores,
+            # norm_idx 1, fp32 state) or the weights pass + K1; operands in the layer's buffers.
+            # A bf16 state: the reference scores from an fp32 copy, as below
+            ref = lay.score_mode == 'reference' and self.opt.get('attention_type', 'scaled_dot') == 'scaled_dot'
+            ns = lay.node_scores(g, x.float() if ref and x.dtype == torch.bfloat16 else x)
+            return ops.squareplus_rhs(g, ns, norm_idx, x, bufs=lay.squareplus_buffers(g, x), **kw)
         if x.dtype == torch.bfloat16:
             # bf16 storage: the per-edge scores' projection reads the bf16 state itself
             # (gnpde_linear_bf16, the same bits as from an fp32 copy); the fork's reference

@@ -792,9 +792,11 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
     be in CSC order) — the backward of the RHS with respect to x.
     stage: a ``Stage`` -> the fused Runge-Kutta outputs are written instead of f
     (returns None).  The adaptive solvers' wide stages (Stage.wide) are fused
-    with plain weights; with weights computed on the fly (RefDstWeights, GatWeights) f is
-    formed first and the stage applied in a second pass (stage_apply)."""
-    if stage is not None and stage.wide and isinstance(w_csr, (RefDstWeights, GatWeights)):
+    with plain weights; with weights computed on the fly (RefDstWeights, GatWeights,
+    RefDstSquareplusWeights) f is formed first and the stage applied in a second pass
+    (stage_apply)."""
+    on_the_fly = (RefDstWeights, GatWeights, RefDstSquareplusWeights)
+    if stage is not None and stage.wide and isinstance(w_csr, on_the_fly):
         f = spmm_rhs(g, w_csr, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
                      add_source=add_source, transpose=transpose)
         stage_apply(stage, f, x, x)
@@ -832,7 +834,7 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
             raise ValueError("spmm_rhs: compacted weights of another grouped CSR")
         items, col, w_csr = w_csr.items, w_csr.col, w_csr.w
     if dt == torch.bfloat16:
-        if isinstance(w_csr, (RefDstWeights, GatWeights)):
+        if isinstance(w_csr, on_the_fly):
             raise ValueError("bf16 storage takes precomputed weights (attn_rhs(..., fuse=False))")
         _lib.call("gnpde_spmm_rhs_bf16", _ptr(items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
                   _ptr(col), _ptr(w_csr), *epi)
@@ -848,6 +850,11 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
         _lib.call("gnpde_attn_gat_rhs_f32", _ptr(plan.items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
                   _ptr(grouped.col), _ptr(w_csr.sp), _ptr(w_csr.m), _ptr(w_csr.rl), w_csr.norm_idx, w_csr.heads,
                   w_csr.slope, *epi)
+    elif isinstance(w_csr, RefDstSquareplusWeights):
+        if transpose:
+            raise ValueError("on-the-fly attention weights aggregate over the CSR only")
+        _lib.call("gnpde_attn_sp_rhs_f32", _ptr(plan.items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
+                  _ptr(grouped.col), _ptr(w_csr.pn), _ptr(w_csr.rl), w_csr.heads, *epi)
     else:
         _lib.call("gnpde_spmm_rhs_f32", _ptr(items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
                   _ptr(col), _ptr(w_csr), *epi)
@@ -1457,6 +1464,159 @@ def edge_attention(g, ns, m, rl, norm_idx):
               ns.mode, ns.heads, ns.dk, _ptr(ns.cs), _ptr(ns.q), _ptr(ns.k), ns.ldqk, ns.p0, ns.p1, _ptr(m), _ptr(rl),
               _ptr(att), _stream(dev))
     return att
+
+
+# --------------------------------------------------------------------------- squareplus normalisation
+# opt['square_plus'] (src/utils.py:129-140): p = squareplus(s - M_b), M_b the maximum over ALL edges
+# and heads of batch element b, normalised per group.  csrc/squareplus.hip; DESIGN.md §6.12.
+class SquareplusState(object):
+    """Per-RHS device operands of the squareplus normaliser: ``M`` [B] fp64 (the global
+    score maximum per batch element), ``amax`` [B] int64 (its first COO position, for the
+    backward), and the values the later passes read: ``pn`` [R,h] fp32 = p per node
+    (reference scores; written by squareplus_stats) or ``sc`` [nnz,h] fp32 = the stored
+    per-edge scores in COO order.  ``ws``: the reduction's scratch.  Built by
+    squareplus_buffers; a layer keeps one per state shape so that captured step graphs keep
+    reading the buffers they were captured with and nothing is read on the host."""
+
+    def __init__(self, M, amax, pn, sc, ws):
+        self.M, self.amax, self.pn, self.sc, self.ws = M, amax, pn, sc, ws
+
+    def tensors(self):
+        return [t for t in (self.M, self.amax, self.pn, self.sc, self.ws) if t is not None]
+
+
+class RefDstSquareplusWeights(object):
+    """Weights K1 computes on the fly (gnpde_attn_sp_rhs_f32): the fork's scaled_dot under
+    destination-grouped squareplus, head-mean per edge from pn [R,h] and rl [R,h]."""
+
+    def __init__(self, pn, rl, heads):
+        self.pn, self.rl, self.heads = pn, rl, int(heads)
+
+
+# The fused squareplus K1 (reference scores, norm_idx 1, fp32 state) against the weights pass +
+# the plain K1: the default is the variant that measured faster on the G-arxiv benchmark graph
+# (tools/squareplus_bench.py, profiles/squareplus_rhs_bench.json, DESIGN.md §6.12: 0.1647 ms fused
+# against 0.1693 per RHS, two heads, C = 128).  GNPDE_SQUAREPLUS_FUSE=1 / 0 forces either.
+SQUAREPLUS_FUSE = os.environ.get("GNPDE_SQUAREPLUS_FUSE", "auto")
+
+
+def squareplus_fuse_default():
+    if SQUAREPLUS_FUSE in ("0", "1"):
+        return SQUAREPLUS_FUSE == "1"
+    return True
+
+
+def _sp_check_mode(ns):
+    if ns.mode in (_lib.SCORE_UNIFORM, _lib.SCORE_GAT):
+        raise ValueError("squareplus: score mode %d is not supported (uniform scores keep the cached 1/outdeg "
+                         "weights; the GAT layer is softmax only)" % ns.mode)
+
+
+def squareplus_buffers(g, mode, heads, dev):
+    """A SquareplusState with buffers for graph ``g`` and score mode ``mode``."""
+    B = g.B
+    M = torch.empty(B, dtype=torch.float64, device=dev)
+    amax = torch.empty(B, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(_lib.fn("gnpde_score_max_workspace_bytes")(B)), dtype=torch.uint8, device=dev)
+    pn = sc = None
+    if mode == _lib.SCORE_REFERENCE:
+        pn = torch.empty(g.R, heads, dtype=torch.float32, device=dev)
+    else:
+        sc = torch.empty(max(g.nnz, 1), heads, dtype=torch.float32, device=dev)
+    return SquareplusState(M, amax, pn, sc, ws)
+
+
+def score_max(g, ns, bufs=None):
+    """The squareplus shift: M [B] fp64 = the maximum score over all edges and heads of each
+    batch element, with its first position (gnpde_score_max_f32; workgroup partials + a
+    final pass, no atomics).  Reference scores: the maximum of the node scores over the rows
+    with an out-edge.  Per-edge modes: one edge pass that also stores the scores.  Returns the
+    SquareplusState (``bufs`` filled in place, or a new one)."""
+    _sp_check_mode(ns)
+    dev = g.csr.col.device
+    sq = bufs if bufs is not None else squareplus_buffers(g, ns.mode, ns.heads, dev)
+    csr = g.csr
+    _lib.call("gnpde_score_max_f32", _ptr(csr.rowptr), _ptr(csr.rowidx), _ptr(csr.col), _ptr(csr.perm), g.B, g.N, g.E,
+              ns.mode, ns.heads, ns.dk, _ptr(ns.cs), _ptr(ns.q), _ptr(ns.k), ns.ldqk, ns.p0, ns.p1, _ptr(sq.M),
+              _ptr(sq.amax), _ptr(sq.sc), _ptr(sq.ws), sq.ws.numel(), _stream(dev))
+    return sq
+
+
+def squareplus_stats(g, ns, sq, norm_idx):
+    """rl [R,h] = 1 / (sum of p over the group + 1e-16), groups = the CSR's rows (norm_idx 0)
+    or the CSC's (norm_idx 1), over the grouped CSR's statistics plan (hub groups in chunks
+    merged in a fixed order).  Reference scores: also writes sq.pn."""
+    _sp_check_mode(ns)
+    grouped = g.csr if norm_idx == 0 else g.csc
+    plan = grouped.stats_plan
+    dev = grouped.col.device
+    H = ns.heads
+    rl = torch.empty(g.R, H, dtype=torch.float32, device=dev)
+    partials = torch.empty(plan.n_slots * H, dtype=torch.float64, device=dev) if plan.n_slots else None
+    _lib.call("gnpde_squareplus_stats_f32", _ptr(plan.items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
+              _ptr(grouped.col), _ptr(grouped.perm), int(norm_idx == 1), g.R, g.N, ns.mode, H, _ptr(ns.cs),
+              _ptr(sq.sc), _ptr(sq.M), _ptr(sq.pn), _ptr(rl), _ptr(partials), _stream(dev))
+    return rl
+
+
+def squareplus_weights(g, ns, sq, rl, norm_idx):
+    """Head-mean squareplus weights in aggregation-CSR order [nnz] (gnpde_squareplus_weights_f32)."""
+    _sp_check_mode(ns)
+    dev = g.csr.col.device
+    w = torch.empty(max(g.nnz, 1), dtype=torch.float32, device=dev)
+    _lib.call("gnpde_squareplus_weights_f32", _ptr(g.csr.rowidx), _ptr(g.csr.col), _ptr(g.csr.perm), g.nnz, g.N,
+              int(norm_idx), ns.mode, ns.heads, _ptr(sq.pn), _ptr(sq.sc), _ptr(sq.M), _ptr(rl), _ptr(w), _stream(dev))
+    return w
+
+
+def squareplus_attention(g, ns, sq, rl, norm_idx):
+    """attention [B,E,h] in COO order under squareplus (gnpde_squareplus_attention_f32)."""
+    _sp_check_mode(ns)
+    dev = g.csr.col.device
+    att = torch.empty(g.B, g.E, ns.heads, dtype=torch.float32, device=dev)
+    _lib.call("gnpde_squareplus_attention_f32", _ptr(g.csr.rowidx), _ptr(g.csr.col), _ptr(g.csr.perm), g.nnz, g.N,
+              int(norm_idx), ns.mode, ns.heads, _ptr(sq.pn), _ptr(sq.sc), _ptr(sq.M), _ptr(rl), _ptr(att),
+              _stream(dev))
+    return att
+
+
+def squareplus_backward(grouped, att, g_att, rl, amax):
+    """dL/ds [B,E,H] (COO, the layout of softmax_backward) of the squareplus normalisation
+    over the groups of ``grouped`` from the saved attention, rl and the arg-max positions
+    amax [B] of the forward: the group term and the max term (gnpde_squareplus_backward_f32)."""
+    _require_gpu(att, "attention", torch.float32)
+    _require_gpu(g_att, "attention grad", torch.float32)
+    _require_gpu(rl, "rl", torch.float32)
+    _require_gpu(amax, "amax", torch.int64)
+    att, g_att = att.contiguous(), g_att.contiguous()
+    B, H = att.shape[0], att.shape[-1]
+    gs = torch.empty_like(att)
+    nb = int(_lib.fn("gnpde_squareplus_backward_workspace_bytes")(B))
+    ws = torch.empty(nb, dtype=torch.uint8, device=att.device)
+    _lib.call("gnpde_squareplus_backward_f32", _ptr(grouped.rowptr), _ptr(grouped.perm), grouped.R, grouped.nnz, B, H,
+              _ptr(att), _ptr(g_att), _ptr(rl), _ptr(amax), _ptr(gs), _ptr(ws), nb, _stream(att.device))
+    return gs
+
+
+def squareplus_rhs(g, ns, norm_idx, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoid=True,
+                   add_source=False, out=None, stage=None, fuse=None, bufs=None):
+    """f = a*(A_att x - x) [+ b x0] with A_att the head-mean squareplus weights: the score
+    maximum, the group statistics, then — reference scores under norm_idx 1 with an fp32
+    state (fuse, default squareplus_fuse_default()) — K1 forming the weights in its gather
+    loop (gnpde_attn_sp_rhs_f32; the same bits as the separate pass), or the weights pass +
+    the plain K1 (per-edge modes, a bf16 state, the adaptive solvers' wide stages and small
+    graphs under the rules of _small_precompute).  No host read."""
+    sq = score_max(g, ns, bufs)
+    rl = squareplus_stats(g, ns, sq, norm_idx)
+    if fuse is None:
+        fuse = squareplus_fuse_default()
+    if fuse and norm_idx == 1 and ns.mode == _lib.SCORE_REFERENCE and x.dtype == torch.float32 and \
+            not _small_precompute(g, stage):
+        w = RefDstSquareplusWeights(sq.pn, rl, ns.heads)
+    else:
+        w = squareplus_weights(g, ns, sq, rl, norm_idx)
+    return spmm_rhs(g, w, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
+                    add_source=add_source, out=out, stage=stage)
 
 
 # --------------------------------------------------------------------------- backward passes

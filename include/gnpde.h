@@ -763,6 +763,71 @@ int gnpde_gat_score_backward_f32(const int32_t* rowidx, const int32_t* col, cons
                                  int64_t heads, const double* sp, float slope, const float* gs, float* ge,
                                  void* stream);
 
+/* ---- squareplus attention normalisation (opt['square_plus'], src/utils.py:129-140) ----
+ *   M_b      = max over all edges e and heads h of s[b,e,h]   (one scalar per batch element)
+ *   p        = 2 / (sqrt(t^2 + 4) - t),  t = s - M_b <= 0     (= (t + sqrt(t^2 + 4)) / 2, stable)
+ *   rl[g,h]  = 1 / (sum of p over the edges of group g + 1e-16)
+ *   att[e,h] = p[e,h] * rl[g(e),h],   w[e] = mean_h att[e,h]
+ * Score modes REFERENCE, DOT, EXP_KERNEL, COSINE, PEARSON; UNIFORM and GAT return
+ * GNPDE_EUNSUPPORTED.  Every sum and maximum has a fixed order (no float atomics).
+ *
+ * gnpde_score_max_f32: M [B] fp64 and amax [B] (optional) = the flat COO position
+ * (b*E + e)*heads + h of the maximum, the smallest one among equal scores (-1 and M = 0
+ * for E = 0).  rowptr / rowidx / col / perm: the aggregation CSR (rows = sources).
+ * REFERENCE: the maximum of the node scores cs [B*N, heads] fp64 over the rows that have
+ * an out-edge.  Per-edge modes: one pass over the edges, which also stores the scores
+ * sc [B*E, heads] fp32 in COO order when sc != NULL (the later passes read them instead of
+ * repeating the dk-long products).  Workgroup partials in the workspace, then a final pass. */
+size_t gnpde_score_max_workspace_bytes(int64_t B);
+int gnpde_score_max_f32(const int32_t* rowptr, const int32_t* rowidx, const int32_t* col, const int32_t* perm,
+                        int64_t B, int64_t N, int64_t E, int mode, int64_t heads, int64_t dk, const double* cs,
+                        const float* q, const float* k, int64_t ldqk, float score_p0, float score_p1, double* M,
+                        int64_t* amax, float* sc, void* workspace, size_t workspace_bytes, void* stream);
+
+/* rl [R, heads] over a plan of the groups' rows (gnpde_plan_build of the CSR, norm_idx 0, or
+ * of the CSC, norm_idx 1 = group_is_dst): items {row, e_begin, e_end, slot}, a hub row's
+ * chunk items store their sums to partials [n_slots * heads] fp64 and heavy {row,
+ * first_slot, n_chunks, -} merges them in a fixed order.  gcol / gperm: the grouped CSR's
+ * col and perm.  REFERENCE: p is per node — pn [R, heads] fp32 = p(cs - M_b) is written
+ * here (the difference in fp64) and the statistics are a gather-sum of it; per-edge modes
+ * read the stored scores sc.  rl of a row without edges is never read.                   */
+int gnpde_squareplus_stats_f32(const int32_t* items, int64_t n_items, const int32_t* heavy, int64_t n_heavy,
+                               const int32_t* gcol, const int32_t* gperm, int group_is_dst, int64_t R, int64_t N,
+                               int mode, int64_t heads, const double* cs, const float* sc, const double* M, float* pn,
+                               float* rl, double* partials, void* stream);
+
+/* Head-mean weights w [nnz] in aggregation-CSR order / attention att [B*E, heads] in COO
+ * order from (M, rl); rowidx / col / perm: the aggregation CSR.  REFERENCE reads pn,
+ * the per-edge modes sc.  The counterparts of gnpde_attn_weights_f32 / gnpde_edge_attention_f32. */
+int gnpde_squareplus_weights_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
+                                 int64_t N, int norm_idx, int mode, int64_t heads, const float* pn, const float* sc,
+                                 const double* M, const float* rl, float* w_out, void* stream);
+int gnpde_squareplus_attention_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
+                                   int64_t N, int norm_idx, int mode, int64_t heads, const float* pn, const float* sc,
+                                   const double* M, const float* rl, float* att, void* stream);
+
+/* K1 with the squareplus weights of the reference scores under destination groups formed
+ * in the gather loop: w_p = (1/heads) sum_h pn[row,h] * rl[col_p,h] (no transcendental per
+ * edge).  Equals gnpde_squareplus_weights_f32 + gnpde_spmm_rhs_f32 bit for bit, in one
+ * pass.  The wide (adaptive-solver) stage epilogue is fused with plain weights only
+ * (GNPDE_EUNSUPPORTED here).  Other arguments as gnpde_spmm_rhs_f32.                      */
+int gnpde_attn_sp_rhs_f32(const int32_t* items, int64_t n_items, int32_t* heavy, int64_t n_heavy, const int32_t* col,
+                          const float* pn, const float* rl, int64_t heads, int64_t C, const float* x, int64_t ldx,
+                          const float* x0, int64_t ldx0, const float* alpha, const float* beta, int flags, float* f,
+                          int64_t ldf, float* partials, int64_t n_slots, const gnpde_stage_epilogue_t* stage,
+                          void* stream);
+
+/* Backward of the squareplus normalisation over the groups of a grouped CSR (COO
+ * [nnz, heads] in and out, nnz = B*E).  With p = att / rl and r = sqrt(t^2 + 4) = p + 1/p:
+ *   gs' = att / r * (g_att - sum over the group of att * g_att)
+ *   gs  = gs' - [position == amax[b]] * (sum over all e, h of gs'[b])    (the max term)
+ * No score is recomputed.                                                                */
+size_t gnpde_squareplus_backward_workspace_bytes(int64_t B);
+int gnpde_squareplus_backward_f32(const int32_t* rowptr, const int32_t* perm, int64_t R, int64_t nnz, int64_t B,
+                                  int heads, const float* att, const float* g_att, const float* rl,
+                                  const int64_t* amax, float* gs, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
