@@ -418,10 +418,13 @@ static __global__ __launch_bounds__(64) void dense_coef_kernel(gnpde_stage_epilo
 // each); inside a slot lane = g*GL + gl: G = SL/GL edges are gathered side by
 // side, each by a group of GL lanes covering the C columns with VEC-wide loads
 // (NCH column passes); U edges per group are in flight per iteration.  The
-// epilogue operands (x_r, x0_r, stage inputs) are loaded before the gathers
-// when NCH <= 2 (PRE) so their latency overlaps the aggregation.  Hub rows are
-// combined in-launch by the chunk that arrives last (hub_claim), and run
-// through the same epilogue as whole rows.
+// epilogue operands (x_r, x0_r, stage inputs) are loaded beside the gathers
+// when NCH <= 2 (PRE) so their latency overlaps the aggregation: ahead of the
+// edge loop, or, in the headline geometry (SCHED below), behind the row's last
+// gathers, with the row's loads issued in the order of its dependence chain
+// and whole pairs of half batches pipelined.  Hub rows are combined in-launch
+// by the chunk that arrives last (hub_claim), and run through the same
+// epilogue as whole rows.
 template <int VEC, int GL, int NCH, int U, int RPW, int STG, class WP, class T = float>
 __global__ __launch_bounds__(256) void agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy,
                                                    int n_heavy, const int* __restrict__ col, WP wp, int C, Epi ep,
@@ -443,15 +446,20 @@ __global__ __launch_bounds__(256) void agg_kernel(const int4* __restrict__ items
   const bool owner = live && slot < 0 && g == 0;
 
   EpiPre<VEC, T, STG> pre[PRE ? NCH : 1];
-  if constexpr (PRE) {
-    if (owner) {
+  // The epilogue operands.  SCHED issues them BEHIND the gathers of the row's last batch:
+  // the loads return in order, and ahead of the column ids they put one more round trip in
+  // front of the gathers.
+  auto prefetch = [&]() {
+    if constexpr (PRE) {
+      if (owner) {
 #pragma unroll
-      for (int ch = 0; ch < NCH; ++ch) {
-        const int cc = (ch * GL + gl) * VEC;
-        if (cc < C) epi_prefetch<VEC, STG, T>(ep, row, cc, pre[ch]);
+        for (int ch = 0; ch < NCH; ++ch) {
+          const int cc = (ch * GL + gl) * VEC;
+          if (cc < C) epi_prefetch<VEC, STG, T>(ep, row, cc, pre[ch]);
+        }
       }
     }
-  }
+  };
 
   float acc[NCH][VEC];
 #pragma unroll
@@ -459,51 +467,200 @@ __global__ __launch_bounds__(256) void agg_kernel(const int4* __restrict__ items
 #pragma unroll
     for (int t = 0; t < VEC; ++t) acc[ch][t] = 0.f;
 
-  for (int e0 = beg; e0 < end; e0 += SL) {
-    const int n = min(SL, end - e0);
+  // The load schedule of DESIGN.md §6.13 (SCHED) is taken by the geometry it was measured
+  // to win on — plain weights, two 32-lane row slots per wavefront, U = 4: fp32 rows of
+  // 65-128 columns, the headline — and by nothing else: the 64-lane geometry lost 6 % to it
+  // (BLEND C = 162 fp32 rk4 step 0.560 -> 0.595 ms) and the attention policies lose
+  // occupancy.  Every other instantiation keeps the one-batch loop below it.
+  constexpr bool SCHED = std::is_same<WP, PlainWeights>::value && sizeof(T) == 4 && VEC == 4 && GL == 32 &&
+                         RPW == 2 && NCH == 1 && U == 4;
+  if constexpr (SCHED) {
+    // The first chunk's column ids go out first: everything else a row needs hangs on them.
+    // The chunk loop below is wave-uniform (it runs to the longest row of the wavefront;
+    // a slot whose row has ended holds n <= 0 edges), so its branches are scalar.
+    const int len = end - beg;
+    int lenmax = 0;
+#pragma unroll
+    for (int s = 0; s < RPW; ++s) lenmax = max(lenmax, __shfl(len, s * SL));
+    lenmax = uniform(lenmax);
     int mc = 0;
-    typename WP::Raw raw{};
-    if (sl < n) {
-      mc = col[e0 + sl];
-      raw = wp.load(row, e0 + sl, mc);
-    }
-    float mw = 0.f;
-    for (int j = 0; j < n; j += G * U) {
-      Packed<VEC, T> v[U][NCH];  // gathered row slices in storage form (bf16: half the registers)
-      float ww[U];
-      int srcl[U];
+    if (sl < len) mc = col[beg + sl];
+
+    // Whole PAIRS of half batches (UP = U/2 edges per group, the registers of one batch of U)
+    // are pipelined — batch b + 1 is issued before batch b is summed, so gathers stay in
+    // flight across batches; the rest of a row (fewer than U edges per group) is one batch.
+    // Whole batches of U with a second buffer measured 2.3 % slower (6 waves per SIMD).
+    constexpr int UP = U / 2;
+    constexpr int B = G * UP;
+    using Slice = Packed<VEC, T>;  // gathered row slices in storage form (bf16: half the registers)
+    const T* __restrict__ xb = as_t<T>(ep.x);
+
+    // One chunk of SL edges per slot.  LAST: the wavefront's last chunk, behind whose last
+    // gathers the epilogue operands go out — not behind the row's first ones, or a long row
+    // would hold them in registers through its pipelined batches.
+    auto chunk = [&](const int e0, auto last_chunk) {
+      constexpr bool LAST = decltype(last_chunk)::value;
+      const int n = min(SL, len - e0);              // this slot's edges in the chunk (<= 0: none)
+      const int nmax = min(SL, lenmax - e0);        // the longest slot's (wave-uniform)
+      const int npair = nmax / (2 * B) * (2 * B);  // its edges in whole pairs of half batches
+      int mcn = 0;                                  // the next chunk's column ids, ahead of this chunk's gathers
+      if (e0 + SL + sl < len) mcn = col[beg + e0 + SL + sl];
+      typename WP::Raw raw{};
+      if (sl < n) raw = wp.load(row, beg + e0 + sl, mc);
+      float mw = 0.f;
+      // the weights of the chunk's edges, finished while its first gathers are in flight
+      auto finish = [&]() {
+        if (sl < n) mw = wp.finish(row, raw);
+      };
+      // acc += w * x over a batch, the edges of a row in CSR order (an edge that is not there
+      // leaves acc as it is: acc is never -0, so the same bits as adding 0 * 0)
+      auto consume = [&](int j, const Slice(&v)[UP][NCH]) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int jj = j + u * G + g;
-        const int src = rs * SL + (jj < n ? jj : 0);
-        srcl[u] = src;
-        const int c = __shfl(mc, src);
-        const T* __restrict__ xr = as_t<T>(ep.x) + (int64_t)c * ep.ldx;
+        for (int u = 0; u < UP; ++u) {
+          const int jj = j + u * G + g;
+          const float ww = __shfl(mw, rs * SL + (jj < n ? jj : 0));
 #pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {
-          const int cc = (ch * GL + gl) * VEC;
-          if (jj < n && cc < C) {
-            load_packed<VEC>(xr + cc, v[u][ch]);
-          } else {
+          for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll
-            for (int t = 0; t < Packed<VEC, T>::W; ++t) v[u][ch].d[t] = 0u;
+            for (int t = 0; t < VEC; ++t)
+              acc[ch][t] = jj < n ? fmaf(ww, unpack(v[u][ch], t), acc[ch][t]) : acc[ch][t];
+        }
+      };
+
+      if (npair > 0) {
+        // In a pipelined batch every lane issues every load — a lane whose slot has no edge
+        // left, or that covers no column, re-reads a slice that is there and its sum skips it —
+        // so no branch lies between the loads and the wait for a batch is counted (vmcnt(N)
+        // with the next batch in flight; behind a branch around a load the compiler waits for
+        // vmcnt(0)).
+        auto issue = [&](int j, Slice(&v)[UP][NCH]) {
+          int c[UP];
+#pragma unroll
+          for (int u = 0; u < UP; ++u) {
+            const int jj = j + u * G + g;
+            c[u] = __shfl(mc, rs * SL + (jj < n ? jj : 0));
+          }
+#pragma unroll
+          for (int u = 0; u < UP; ++u) {
+            const T* __restrict__ xr = xb + (int64_t)c[u] * ep.ldx;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+              const int cc = (ch * GL + gl) * VEC;
+              load_packed<VEC>(xr + (cc < C ? cc : 0), v[u][ch]);
+            }
+          }
+        };
+        Slice va[UP][NCH], vb[UP][NCH];
+        issue(0, va);
+        finish();
+        int j = 0;
+#pragma unroll 1  // a chunk holds at most SL / B batches: unrolled, all of them would be in flight
+        for (; j + 2 * B < npair; j += 2 * B) {  // batch j is in flight in va
+          issue(j + B, vb);
+          consume(j, va);
+          issue(j + 2 * B, va);
+          consume(j + B, vb);
+        }
+        issue(j + B, vb);
+        if constexpr (LAST)
+          if (npair == nmax) prefetch();
+        consume(j, va);
+        consume(j + B, vb);
+      }
+      // The edges behind the whole pairs (at most one batch of U per group; of a short row,
+      // all of them): only the gathers that are there are issued, all before the first is summed.  This loader and its FMA block repeat issue() and
+      // consume() above on purpose: one buffer variable written by both a branch-free and a
+      // predicated loader comes out of the register allocation with copies of single dwords
+      // behind the loads, each a vmcnt(0).
+      if (npair < nmax) {
+        const int j = npair;
+        Slice v[U][NCH];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int jj = j + u * G + g;
+          const int c = __shfl(mc, rs * SL + (jj < n ? jj : 0));
+          const T* __restrict__ xr = xb + (int64_t)c * ep.ldx;
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch) {
+            const int cc = (ch * GL + gl) * VEC;
+            if (jj < n && cc < C) {
+              load_packed<VEC>(xr + cc, v[u][ch]);
+            } else {
+#pragma unroll
+              for (int t = 0; t < Slice::W; ++t) v[u][ch].d[t] = 0u;
+            }
           }
         }
+        if (j == 0) finish();
+        if constexpr (LAST)
+          prefetch();
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int jj = j + u * G + g;
+          const float ww = __shfl(mw, rs * SL + (jj < n ? jj : 0));
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+            for (int t = 0; t < VEC; ++t)
+              acc[ch][t] = jj < n ? fmaf(ww, unpack(v[u][ch], t), acc[ch][t]) : acc[ch][t];
+        }
       }
-      // the weights of this batch of edges, finished while its first gathers are in flight
-      if (j == 0 && sl < n) mw = wp.finish(row, raw);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int jj = j + u * G + g;
-        const float wsl = __shfl(mw, srcl[u]);
-        ww[u] = jj < n ? wsl : 0.f;
+      mc = mcn;
+    };
+    int e0 = 0;
+    for (; e0 + SL < lenmax; e0 += SL) chunk(e0, std::false_type{});
+    if (lenmax > 0)
+      chunk(e0, std::true_type{});
+    else
+      prefetch();  // a wavefront of rows without edges
+  } else {
+    prefetch();  // ahead of the aggregation
+    for (int e0 = beg; e0 < end; e0 += SL) {
+      const int n = min(SL, end - e0);
+      int mc = 0;
+      typename WP::Raw raw{};
+      if (sl < n) {
+        mc = col[e0 + sl];
+        raw = wp.load(row, e0 + sl, mc);
       }
+      float mw = 0.f;
+      for (int j = 0; j < n; j += G * U) {
+        Packed<VEC, T> v[U][NCH];  // gathered row slices in storage form (bf16: half the registers)
+        float ww[U];
+        int srcl[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u)
+        for (int u = 0; u < U; ++u) {
+          const int jj = j + u * G + g;
+          const int src = rs * SL + (jj < n ? jj : 0);
+          srcl[u] = src;
+          const int c = __shfl(mc, src);
+          const T* __restrict__ xr = as_t<T>(ep.x) + (int64_t)c * ep.ldx;
 #pragma unroll
-        for (int ch = 0; ch < NCH; ++ch)
+          for (int ch = 0; ch < NCH; ++ch) {
+            const int cc = (ch * GL + gl) * VEC;
+            if (jj < n && cc < C) {
+              load_packed<VEC>(xr + cc, v[u][ch]);
+            } else {
 #pragma unroll
-          for (int t = 0; t < VEC; ++t) acc[ch][t] = fmaf(ww[u], unpack(v[u][ch], t), acc[ch][t]);
+              for (int t = 0; t < Packed<VEC, T>::W; ++t) v[u][ch].d[t] = 0u;
+            }
+          }
+        }
+        // the weights of this batch of edges, finished while its first gathers are in flight
+        if (j == 0 && sl < n) mw = wp.finish(row, raw);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int jj = j + u * G + g;
+          const float wsl = __shfl(mw, srcl[u]);
+          ww[u] = jj < n ? wsl : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) acc[ch][t] = fmaf(ww[u], unpack(v[u][ch], t), acc[ch][t]);
+      }
     }
   }
   // combine the G edge groups of each slot

@@ -424,8 +424,9 @@ __device__ __forceinline__ void pack_into(const float (&v)[VEC], Packed<VEC, T>&
   }
 }
 
-// Epilogue operands of one row slice, loaded ahead of the aggregation so their
-// latency overlaps the gathers (they depend only on the row).
+// Epilogue operands of one row slice, loaded beside the aggregation's gathers so
+// their latency overlaps them (they depend only on the row; agg_kernel issues them
+// ahead of the edge loop or, in its headline geometry, behind the row's last gathers).
 // STG = the stage epilogue an instantiation is compiled for:
 //   0: store f;
 //   1: one stage output, at most kStagePre shared operands, no dot / error term
