@@ -60,6 +60,16 @@ inline int check_stage(const gnpde_stage_epilogue_t& st) {
   for (int j = 0; j < st.nk; ++j) GNPDE_REQUIRE(st.k[j] != nullptr, GNPDE_EINVAL, "stage: k[%d] is NULL", j);
   for (int i = 0; i < st.n_out; ++i) GNPDE_REQUIRE(st.o[i].out, GNPDE_EINVAL, "stage: output %d is NULL", i);
   GNPDE_REQUIRE(st.f_out || st.n_out > 0 || st.err_rows, GNPDE_EINVAL, "stage: the epilogue stores nothing");
+  // An output may be its base or a k operand in place (every element is read by the lane that
+  // writes it, before its store; all stage arrays share one leading dimension and type) —
+  // but not through out_rows, which stores a row somewhere else than it was read.
+  if (st.out_rows) {
+    for (int i = 0; i < st.n_out; ++i) {
+      GNPDE_REQUIRE(st.o[i].out != st.o[i].base, GNPDE_EINVAL, "stage: output %d aliases its base under out_rows", i);
+      for (int j = 0; j < st.nk; ++j)
+        GNPDE_REQUIRE(st.o[i].out != st.k[j], GNPDE_EINVAL, "stage: output %d aliases k[%d] under out_rows", i, j);
+    }
+  }
   GNPDE_REQUIRE(!st.dot_rows || st.dot_with, GNPDE_EINVAL, "stage: dot_rows without dot_with");
   // a dot term beside error rows or more than kStagePre operands: the wide epilogue (STG 4)
   // carries it as a second row sum (the adaptive adjoint's alpha integrand, gnpde.integrator)

@@ -149,13 +149,15 @@ def _fusable(func, y0, combine):
 RHS_PER_STEP = {'euler': 1, 'midpoint': 2, 'rk4': 4}
 
 
-def _fused_step(method, func, t0, dt, t1, y0, ws, out=None, out_rows=None):
+def _fused_step(method, func, t0, dt, t1, y0, ws, out=None, out_rows=None, inplace=False):
     """One grid step with the stage combinations fused into the RHS epilogues
     (gnpde_stage_epilogue_t): same arithmetic as _fixed_step, ~7 fewer passes
     over the state per rk4 step and no separate combine launches.  ``out``:
     the buffer that receives y1 (default: a new tensor); ``out_rows`` (int32
     [R]): y1's row r is stored at row out_rows[r] of ``out`` (the last step of
-    a solve run in a node renumbering writes the caller's numbering)."""
+    a solve run in a node renumbering writes the caller's numbering).
+    ``inplace`` (rk4): the step in three live buffers — y1 overwrites y0 when no
+    ``out`` is given, and y0 is left alone otherwise; the same bits either way."""
     y0 = y0.contiguous()
     if method == 'euler':
         y1 = torch.empty_like(y0) if out is None else out
@@ -176,6 +178,20 @@ def _fused_step(method, func, t0, dt, t1, y0, ws, out=None, out_rows=None):
         #   y1 = y + dt/8 (k1 + 3k2 + 3k3 + k4) = (6 x3 + 3 x4 - y + dt k4) / 8
         # 8 state passes per step besides the gathers (one write per stage,
         # reads of y, x2, y + x3), where storing k's and an accumulator takes 15.
+        if inplace:
+            # The step never needs more than three live buffers (y, a, b: 260 MB on G-arxiv
+            # against 433 MB for five, beside a 256 MiB Infinity Cache): x4 is written over x2
+            # and y1 over y — each read only as the own-row operand of the row being written,
+            # by the lane that writes it, before its store (ops.Stage: an output may alias an
+            # operand).  Same combinations, same operand order: the same bits.
+            a, b = ws.get('a', y0), ws.get('b', y0)
+            y1 = y0 if out is None else out
+            func.rhs_stage(t0, y0, ops.Stage(outs=[(a, y0, 1.0, dt / 3.0, [])]))
+            func.rhs_stage(t0 + dt / 3.0, a, ops.Stage(outs=[(b, a, -1.0, dt, [(y0, 2.0)])]))
+            func.rhs_stage(t0 + dt * 2.0 / 3.0, b, ops.Stage(outs=[(a, b, -1.0, dt, [(a, 2.0)])]))
+            func.rhs_stage(t1, a, ops.Stage(outs=[(y1, a, 0.375, dt * 0.125, [(b, 0.75), (y0, -0.125)])],
+                                            out_rows=out_rows))
+            return y1
         x2, x3, x4 = ws.get('a', y0), ws.get('b', y0), ws.get('c', y0)
         y1 = torch.empty_like(y0) if out is None else out
         func.rhs_stage(t0, y0, ops.Stage(outs=[(x2, y0, 1.0, dt / 3.0, [])]))
@@ -220,6 +236,15 @@ GRAPH_BLOCK = int(os.environ.get('GNPDE_GRAPH_BLOCK', '64'))
 # Set to a list to receive (start_event, end_event, n_rhs) per graph replay
 # (bench.py's per-launch roofline timing); None in normal use.
 replay_events = None
+# The no-grad fixed-grid rk4 solve keeps its state in one buffer and steps in place
+# (_fused_step(inplace=True): three live buffers instead of five) for modules that do not
+# place their own state (alloc_state: the row-sharded classes keep the ping-pong scheme).
+# GNPDE_RK4_INPLACE=0 keeps the ping-pong scheme everywhere; results do not depend on it.
+RK4_INPLACE = os.environ.get('GNPDE_RK4_INPLACE', '1') != '0'
+
+
+def _steps_inplace(method, func, y):
+    return RK4_INPLACE and method == 'rk4' and y.is_cuda and getattr(func, 'alloc_state', None) is None
 
 
 def _pow2_blocks(k, cap):
@@ -270,15 +295,15 @@ def _state_pool(func, y):
 
 class _StepGraphs(object):
     """Captured blocks of fixed-dt grid steps over a _StatePool: graph (s, p)
-    runs s steps starting from bufs[p] (ping-ponging, so it ends in bufs[p ^ (s & 1)]);
-    captured on first use.  The launches are those of the eager fused step (same
+    runs s steps starting from bufs[p] (ping-ponging, so it ends in bufs[p ^ (s & 1)];
+    ``inplace``: in bufs[p] itself); captured on first use.  The launches are those of the eager fused step (same
     kernels, same arguments, same bits).  ``warm`` is False until one eager step
     of this entry has run: every per-graph structure (CSR, plans, cached weights,
     scratch) is built by an eager call before anything is captured, so nothing
     synchronises inside a capture."""
 
-    def __init__(self, method, func, dt, pool):
-        self.method, self.dt, self.pool = method, dt, pool
+    def __init__(self, method, func, dt, pool, inplace=False):
+        self.method, self.dt, self.pool, self.inplace = method, dt, pool, inplace
         self.n_rhs = RHS_PER_STEP[method]
         self.graphs = {}
         self.mempool = None
@@ -292,6 +317,9 @@ class _StepGraphs(object):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self.mempool):
                 for k in range(s):
+                    if self.inplace:
+                        _fused_step(self.method, func, 0.0, self.dt, self.dt, bufs[p], ws, inplace=True)
+                        continue
                     i = p ^ (k & 1)
                     _fused_step(self.method, func, 0.0, self.dt, self.dt, bufs[i], ws, out=bufs[1 - i])
             if self.mempool is None:
@@ -300,6 +328,10 @@ class _StepGraphs(object):
                 func.nfe = nfe  # capture records launches, it evaluates nothing
             self.graphs[(s, p)] = g
         return g
+
+    def end(self, s, p):
+        """The parity the state is in after s steps from bufs[p]."""
+        return p if self.inplace else p ^ (s & 1)
 
     def replay(self, func, s, p):
         """Replay s steps from bufs[p]; counts the RHS evaluations like the eager
@@ -315,7 +347,7 @@ class _StepGraphs(object):
             replay_events.append((ev0, ev1, s * self.n_rhs))
         else:
             g.replay()
-        return p ^ (s & 1)
+        return self.end(s, p)
 
 
 # Captured step graphs kept per RHS module between odeint calls (one entry per
@@ -764,6 +796,7 @@ def _solve_fused(func, y0, t_h, steps, method, graph):
     sol = torch.empty((len(t_h),) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
     pool = _state_pool(func, y0)
     bufs, ws = pool.bufs, pool.ws
+    inplace = _steps_inplace(method, func, y0)
     _entry_copy(y0.contiguous(), bufs[0], sol[0], lay.order if lay is not None else None)
     if lay is not None:
         func._layout = lay
@@ -775,10 +808,11 @@ def _solve_fused(func, y0, t_h, steps, method, graph):
             key = _graph_cache_key(func, method, bufs[0], state)
             dt0 = steps[0][1] - steps[0][0]
             hit = _GRAPH_CACHE.get(func) if key is not None else None
-            if hit is not None and hit[0] == key and hit[1].dt == dt0 and hit[1].pool is pool:
+            if (hit is not None and hit[0] == key and hit[1].dt == dt0 and hit[1].pool is pool
+                    and hit[1].inplace == inplace):
                 sg = hit[1]
             else:
-                sg = _StepGraphs(method, func, dt0, pool)
+                sg = _StepGraphs(method, func, dt0, pool, inplace)
                 if key is not None:
                     _GRAPH_CACHE[func] = (key, sg, state)
         p = 0      # the state is in bufs[p]
@@ -792,15 +826,17 @@ def _solve_fused(func, y0, t_h, steps, method, graph):
             m = i
             while m < n - 1 and steps[m][1] < t_h[j]:
                 m += 1
-            p = _advance(func, method, steps, i, m, p, pool, sg)
+            p = _advance(func, method, steps, i, m, p, pool, sg, inplace)
             ta, tb = steps[m]
             if m == n - 1 and j == len(t_h) - 1 and t_h[j] == tb:
                 # the last step writes the result in the caller's numbering
                 _fused_step(method, func, ta, tb - ta, tb, bufs[p], ws, out=sol[j],
-                            out_rows=lay.order32 if lay is not None else None)
+                            out_rows=lay.order32 if lay is not None else None, inplace=inplace)
                 j += 1
                 break
-            p = _advance(func, method, steps, m, m + 1, p, pool, sg)
+            # an output time inside the step is interpolated from the state before it: that
+            # step keeps its input (the ping-pong form)
+            p = _advance(func, method, steps, m, m + 1, p, pool, sg, inplace and t_h[j] == tb)
             ya, yb = bufs[1 - p], bufs[p]
             while j < len(t_h) and tb >= t_h[j]:
                 if t_h[j] == tb:
@@ -814,8 +850,8 @@ def _solve_fused(func, y0, t_h, steps, method, graph):
     return sol
 
 
-def _advance(func, method, steps, i, m, p, pool, sg):
-    """Run steps i .. m-1 from bufs[p]; returns the parity the state ends in.
+def _advance(func, method, steps, i, m, p, pool, sg, inplace=False):
+    """Run steps i .. m-1 from bufs[p] (``inplace``: in bufs[p]); returns the parity the state ends in.
     Steps of the captured dt go through block graphs (binary decomposition),
     others — and every step while the module is not warm or too close to its
     max_nfe — run eagerly (a MaxNFEException is then raised at the exact call)."""
@@ -834,8 +870,8 @@ def _advance(func, method, steps, i, m, p, pool, sg):
             q = 0
             for s in _pow2_blocks(k, GRAPH_BLOCK):
                 sg.graph(func, s, q)
-                q ^= s & 1
-        if sg is not None and sg.warm and dt == sg.dt:
+                q = sg.end(s, q)
+        if sg is not None and sg.warm and dt == sg.dt and sg.inplace == inplace:
             k = 1
             while i + k < m and steps[i + k][1] - steps[i + k][0] == dt:
                 k += 1
@@ -844,10 +880,13 @@ def _advance(func, method, steps, i, m, p, pool, sg):
                     p = sg.replay(func, s, p)
                 i += k
                 continue
-        _fused_step(method, func, ta, dt, tb, bufs[p], ws, out=bufs[1 - p])
+        if inplace:
+            _fused_step(method, func, ta, dt, tb, bufs[p], ws, inplace=True)
+        else:
+            _fused_step(method, func, ta, dt, tb, bufs[p], ws, out=bufs[1 - p])
+            p = 1 - p
         if sg is not None and dt == sg.dt:
             sg.warm = True
-        p = 1 - p
         i += 1
     return p
 

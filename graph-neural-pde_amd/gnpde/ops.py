@@ -575,9 +575,11 @@ class Stage(object):
     ``f_out`` receives f (optional); each entry of ``outs`` is
     (out, base, cb, cf, [(k_j, c_j), ...]) meaning out = cb*base + cf*f + sum_j c_j*k_j.
     ``base`` may be None, the RHS input x, or ``out`` itself (in place).  No
-    output may alias the RHS input.  The k operands of all outputs (and of the
-    error term) are collected into the stage's shared operand table, each
-    distinct tensor once (read once per row by the kernel).
+    output may alias the RHS input.  An output may be the same array as its base or
+    as one of the k operands (same dtype and size: every element is read by the lane
+    that writes it, before its store), but only without ``out_rows``.  The k operands
+    of all outputs (and of the error term) are collected into the stage's shared
+    operand table, each distinct tensor once (read once per row by the kernel).
 
     ``err`` (the adaptive solvers' embedded-pair error rows): (rows, (base, cb,
     cf, [(k_j, c_j)...]), y0, y1_out, atol, rtol) -> rows[r] = sum_c (e / tol)^2
@@ -691,6 +693,15 @@ class Stage(object):
         for i, (out, base, cb, cf, terms) in enumerate(self.outs):
             if x_input is not None and out.data_ptr() == x_input.data_ptr():
                 raise ValueError("a stage output may not alias the RHS input")
+            if out.data_ptr() in slot or (base is not None and out.data_ptr() == base.data_ptr()):
+                # in place: every element is read by the lane that writes it, before its store
+                if self.out_rows is not None:
+                    raise ValueError("a stage output that aliases its base or an operand cannot take out_rows")
+                for t in [base] + ks:
+                    if t is not None and t.data_ptr() == out.data_ptr() and (t.dtype != out.dtype
+                                                                             or t.numel() != out.numel()):
+                        raise ValueError("a stage output may alias its base or an operand only as the same array "
+                                         "(dtype and size)")
             fill(st.o[i], out, base, cb, cf, terms)
         if self.err is not None:
             rows, (base, cb, cf, terms), y0, y1_out, atol, rtol = self.err

@@ -207,6 +207,11 @@ size_t gnpde_plan_workspace_bytes(int64_t R);
  * epilogue is reused) or equal to o[i].out (in-place accumulation).  Every
  * array has the leading dimension ldf of the RHS output.  No output may alias
  * the RHS input x (other rows of x are still being gathered).
+ * Aliasing rule: an output may be the same array as its base or as a k operand
+ * (the whole array: same pointer, leading dimension and element type) — every
+ * element is read by the lane that stores it, before its store — but only
+ * without out_rows (GNPDE_EINVAL otherwise: a row would be stored where another
+ * lane still reads).  Partly overlapping arrays are never allowed.
  * out_rows (NULL = identity): the o[i].out stores of row r go to row
  * out_rows[r] instead (base, k and f_out stay at row r) — the last step of a
  * solve run in a renumbered node order writes its result straight into the

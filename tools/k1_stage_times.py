@@ -1,0 +1,23 @@
+#!/usr/bin/env python
+"""Per-stage times of the headline K1 in a rocprofv3 kernel trace of
+`bench.py --gpus 1 --steps K --warmup W`: the last 4 K dispatches of the fused-stage
+kernel are the timed solve's, four per rk4 step in stage order.
+python tools/k1_stage_times.py <run_kernel_trace.csv> [K]"""
+import csv
+import statistics
+import sys
+
+NAME = "void gnpde::agg_kernel<4, 32, 1, 4, 2, 1, gnpde::PlainWeights, float>"
+
+rows = list(csv.DictReader(open(sys.argv[1])))
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if r["Kernel_Name"].startswith(NAME))
+print("K1 fused-stage dispatches: %d | name: %s" % (len(ev), NAME))
+ev = ev[-4 * steps:]
+for s in range(4):
+    d = [(e - b) / 1e3 for b, e in ev[s::4]]
+    print("stage %d: mean %.1f us  median %.1f  min %.1f  max %.1f  (n=%d)" % (
+        s + 1, statistics.mean(d), statistics.median(d), min(d), max(d), len(d)))
+span = (ev[-1][1] - ev[0][0]) / 1e3
+busy = sum(e - b for b, e in ev) / 1e3
+print("span of the last %d launches %.1f us, busy %.1f us (%.1f %%)" % (len(ev), span, busy, 100.0 * busy / span))
