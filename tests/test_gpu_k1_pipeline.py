@@ -1,10 +1,17 @@
-"""K1's pipelined edge loop (csrc/aggregate.hpp): rows at every boundary of the loop's
-schedule — the edge batches, the 32- and 64-edge column chunks of a row slot, the hub
-chunks — several of each per wavefront, the last row slot of the launch empty.
+"""K1's pipelined edge loop (csrc/aggregate.hpp) on a small graph: rows of 0 .. 700 edges — around
+the 4- and 8-edge batches, and long rows — several of each per wavefront, the last row slot of
+the launch empty.
+
+The graph has fewer than ops.SMALL_GRAPH_ROWS rows and is built with the default split, so every
+row of more than ops.SMALL_CHUNK = 16 edges is a hub of chunks of at most 16 edges: what runs here
+is the loop's first 32-edge chunk of a row slot (always its LAST one), the short batches, and the
+in-launch hub combine of 2 .. 44 chunks.  The second and later chunks of a row slot, the
+next-chunk column prefetch and the 256-edge items of the large graphs are run by
+tests/test_gpu_long_items.py, on the same row lengths at chunk = 256.
 
 The schedule is not allowed to move a bit: tests/golden/k1_pipeline/rk4_c128_rows.npy holds
 64 rows of the three-step rk4 result at C = 128 as the library computed them BEFORE the
-loop was pipelined (edges of a row summed in CSR order, acc = fmaf(w, x, acc)).
+loop was pipelined (edges of a row summed in CSR order, acc = fmaf(w, x, acc)), at this split.
 """
 import os
 
@@ -25,8 +32,9 @@ BF16_ROUND = 4e-3  # bf16 RHS against the reference on the same bf16-rounded inp
 
 GOLDEN_ROWS = os.path.join(GOLDEN, "k1_pipeline", "rk4_c128_rows.npy")
 
-# edges per row: empty, self loop only, around the 4- and 8-edge batches, the 32- / 64-edge
-# chunks of a row slot, the 256-edge hub chunk, and a hub of several chunks
+# edges per row: empty, self loop only, around the 4- and 8-edge batches and the 16-edge split, and
+# hubs of 2 .. 44 chunks (at this graph's 16-edge split no item reaches a second 32-edge chunk of a
+# row slot; the lengths around 32, 64 and 256 are boundaries at chunk = 256: test_gpu_long_items.py)
 LENGTHS = (0, 1, 2, 3, 4, 5, 7, 8, 9, 31, 32, 33, 63, 64, 65, 255, 256, 257, 700)
 ALPHA, BETA = 0.3, -0.2
 STEPS, DT = 3, 0.1
@@ -48,6 +56,7 @@ class Case(object):
         if g.csr.plan.n_items % 2 == 0:  # an odd item count: the last wavefront's last row slot is empty
             lens = np.concatenate([lens, [0]])
             g = self._graph(lens, rng)
+        assert g.chunk == ops.SMALL_CHUNK  # the small-graph split: the golden rows were recorded at it
         assert g.csr.plan.n_items % 2 == 1 and g.csr.plan.n_heavy >= 3
         self.graph, self.lens, self.N = g, lens, lens.size
         self.w = rng.uniform(0.1, 1.0, size=(1, self.ei.shape[2])).astype(np.float32)
