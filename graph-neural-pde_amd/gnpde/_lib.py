@@ -97,6 +97,8 @@ SIGNATURES = {
     "gnpde_seg_long_pass_edges": (_int, [_i64]),
     "gnpde_linear_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "gnpde_linear_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "gnpde_linear_rhs_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64,
+                                    ctypes.POINTER(StageEpilogue), _vp]),
     "gnpde_linear_wgrad_workspace_bytes": (_size, [_i64, _i64, _i64]),
     "gnpde_linear_wgrad_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _size, _vp]),
     "gnpde_keysum_workspace_bytes": (_size, [_i64, _i64, _i64, _i64]),

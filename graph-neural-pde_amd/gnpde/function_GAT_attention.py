@@ -30,10 +30,26 @@ so [sl | sr] = x U with U [C, 2h] = W folded with a.  One RHS here is:
    graph (ops.gat_fuse_default; GNPDE_GAT_FUSE=1 / 0 forces either).
 
 ``Wout`` is dead for ``mix_features=False`` (:38 is the only use) and is never
-read; the parameter exists for state_dict compatibility and gets no gradient.
-``mix_features=True`` is out of scope and ``multi_modal=True`` calls
-``torch.nn.softmax``, which does not exist (:121): both raise
-NotImplementedError.
+read there; the parameter exists for state_dict compatibility and gets no gradient.
+``multi_modal=True`` calls ``torch.nn.softmax``, which does not exist (:121), and
+raises NotImplementedError.
+
+``mix_features=True`` (the value projection, :29-38) runs when the option dict also
+sets ``opt['gnpde_gat_mix_features'] = True`` (NotImplementedError without the key,
+fp32 states only).  The reference aggregates the projected features per head and maps
+them back, wx = mean_h(A_h (x W)), ax = wx Wout.  Every head's attention multiplies
+the whole wx (not a per-head slice), so the head mean commutes with the product and
+
+    f = a ((A_mean (x W)) Wout - x) + b x0
+
+with the head-mean attention A_mean of steps 1-3.  One RHS is then: the node scores
+and statistics as above (still from x U: wx is not needed for them), wx = x W
+(gnpde_linear_f32), z = A_mean wx by the GAT-weight K1 at width attention_dim with no
+epilogue, and gnpde_linear_rhs_f32: z Wout with the RHS epilogue fused.  The kernel also
+fuses the fixed-grid Runge-Kutta stage combination (the same bits as f followed by
+gnpde_stage_apply_f32); the solvers' stages take the two passes, which measured faster
+(DESIGN.md §6.15), as the adaptive stages do.
+W^T and Wout^T are cached per parameter version (stable buffers for captured graphs).
 
 Gradients: with autograd recording the layer's forward is ``_GatEdgeAttention``
 — the same forward kernels, and a backward of graph passes: edge-softmax
@@ -45,7 +61,9 @@ composes it with the Laplacian RHS autograd, as ODEFuncTransformerAtt does.
 Pinned by fp64 autograd fixtures of the reference layer's forward
 (tests/golden/gat/gatgrad_*.npz; tests/golden/gen_golden_gat.py says why the dense
 product is rebuilt there: torch's backward of the reference's permuted sparse
-tensor is not the derivative of its forward).
+tensor is not the derivative of its forward).  Under mix_features the RHS autograd is
+``_GatMixRHS`` instead of the Laplacian one: gradients also reach ``Wout``, and ``W``
+through the value path (tests/golden/gat_mix/gatmixgrad_*.npz).
 """
 import torch
 from torch import nn
@@ -56,8 +74,10 @@ from .utils import MaxNFEException
 
 
 def _check_supported(opt):
-    if opt.get('mix_features', False):
-        raise NotImplementedError("gnpde: function 'GAT' with mix_features=True is out of scope")
+    if opt.get('mix_features', False) and not opt.get('gnpde_gat_mix_features', False):
+        raise NotImplementedError("gnpde: function 'GAT' with mix_features=True (the value projection, "
+                                  "function_GAT_attention.py:29-38) is opt-in: set "
+                                  "opt['gnpde_gat_mix_features'] = True to select it")
     if opt.get('multi_modal', False):
         raise NotImplementedError("gnpde: multi_modal is broken in the reference (torch.nn.softmax, "
                                   "function_GAT_attention.py:121) and out of scope")
@@ -111,6 +131,83 @@ class _GatEdgeAttention(torch.autograd.Function):
         return gx, gW.reshape(W.shape).to(W.dtype), ga.reshape(a.shape).to(a.dtype), None, None, None
 
 
+class _GatProject(torch.autograd.Function):
+    """wx = x W (:123) on the matrix cores, with its backward (mix_features)."""
+
+    @staticmethod
+    def forward(ctx, x, W, Wt):
+        ctx.save_for_backward(x, W)
+        return ops.linear(x.detach(), Wt)[0].view(tuple(x.shape[:-1]) + (W.shape[1],))
+
+    @staticmethod
+    def backward(ctx, g_wx):
+        x, W = ctx.saved_tensors
+        g_wx = g_wx.contiguous()
+        gx = ops.linear(g_wx, W.detach())[0].view(x.shape) if ctx.needs_input_grad[0] else None
+        gW = ops.linear_wgrad(x.detach(), g_wx) if ctx.needs_input_grad[1] else None
+        return gx, gW, None
+
+
+class _GatMixRHS(torch.autograd.Function):
+    """f = a ((A_mean (x W)) Wout - x) [+ b x0] as a function of (x, alpha, beta,
+    attention, W, Wout): the forward kernels of the no-grad path, and a backward of
+    existing passes.  With g = dL/df and gh = a g:
+      gWout = z^T gh, g_z = gh Wout^T, g_wx = A_mean^T g_z (K1 over the CSC),
+      g_att[e,h] = <g_z[src], wx[dst]> / H, gW = x^T g_wx, g_x = -gh + g_wx W^T,
+      g_alpha, g_beta by fp64 dots (as the Laplacian RHS)."""
+
+    @staticmethod
+    def forward(ctx, x, alpha_train, beta_train, att, W, Wout, g, Wt, Wot, x0, alpha_sigmoid, add_source):
+        xd, ad = x.detach(), att.detach()
+        wx = ops.linear(xd, Wt)[0].view(g.B, g.N, W.shape[1])
+        z = ops.spmm_rhs(g, g.gather_weights(ad), wx, rhs=False)
+        f = ops.linear_rhs(z, Wot, xd, x0=x0, alpha=alpha_train.detach(), beta=beta_train.detach(), rhs=True,
+                           alpha_sigmoid=alpha_sigmoid, add_source=add_source)
+        ctx.save_for_backward(x, alpha_train, beta_train, att, W, Wout, wx, z)
+        ctx.g, ctx.Wot, ctx.x0 = g, Wot, x0
+        ctx.alpha_sigmoid, ctx.add_source = alpha_sigmoid, add_source
+        return f
+
+    @staticmethod
+    def backward(ctx, gf):
+        x, alpha_train, beta_train, att, W, Wout, wx, z = ctx.saved_tensors
+        g = ctx.g
+        gf = gf.contiguous()
+        x, W, Wout, ad = x.detach(), W.detach(), Wout.detach(), att.detach()
+        al = alpha_train.detach()
+        a = torch.sigmoid(al) if ctx.alpha_sigmoid else al
+        gh = (a.float() * gf).contiguous()
+        need = ctx.needs_input_grad
+        gx = ga = gb = gatt = gW = gWout = None
+        if need[5]:
+            gWout = ops.linear_wgrad(z, gh).to(Wout.dtype)                     # [att, C] = z^T gh
+        if need[0] or need[3] or need[4]:
+            g_z = ops.linear(gh, Wout)[0]                                      # [R, att] = gh Wout^T
+            if need[3]:
+                gatt = ops.sddmm(g, g_z, wx, heads=att.shape[2]).view(att.shape)
+            if need[0] or need[4]:
+                g_wx = ops.spmm_rhs(g, g.gather_weights(ad, transpose=True), g_z.view(wx.shape), rhs=False,
+                                    transpose=True)
+                if need[4]:
+                    gW = ops.linear_wgrad(x, g_wx).to(W.dtype)                 # [C, att] = x^T g_wx
+                if need[0]:
+                    gx = ops.linear(g_wx, W)[0].view(x.shape) - gh             # g_wx W^T - gh
+        if need[1]:
+            one = torch.ones((), dtype=torch.float32, device=x.device)
+            d = ops.linear_rhs(z, ctx.Wot, x, alpha=one, rhs=True, alpha_sigmoid=False)   # ax - x
+            s = ops.dot(gf, d).to(alpha_train.dtype)  # fp64 accumulation, fixed order
+            if ctx.alpha_sigmoid:
+                sg = torch.sigmoid(al)
+                s = s * sg * (1 - sg)
+            ga = s.reshape(alpha_train.shape)
+        if need[2]:
+            if ctx.add_source:
+                gb = ops.dot(gf, ctx.x0.float()).to(beta_train.dtype).reshape(beta_train.shape)
+            else:
+                gb = torch.zeros_like(beta_train)
+        return gx, ga, gb, gatt, gW, gWout, None, None, None, None, None, None
+
+
 class SpGraphAttentionLayer(nn.Module):
     """Sparse GAT layer, src/function_GAT_attention.py:74-139 (https://arxiv.org/abs/1710.10903)."""
 
@@ -127,6 +224,7 @@ class SpGraphAttentionLayer(nn.Module):
         assert self.attention_dim % self.h == 0, "Number of heads must be a factor of the dimension size"
         self.d_k = self.attention_dim // self.h
         _check_supported(opt)
+        self.mix = bool(opt.get('mix_features', False))
         self.W = nn.Parameter(torch.zeros(size=(in_features, self.attention_dim)))
         nn.init.xavier_normal_(self.W.data, gain=1.414)
         self.Wout = nn.Parameter(torch.zeros(size=(self.attention_dim, self.in_features)))
@@ -137,6 +235,7 @@ class SpGraphAttentionLayer(nn.Module):
         self._graph = None
         self._graph_key = None
         self._folded = None  # (param versions, (W, a flat, the device scratch holding U))
+        self._transposed = None  # (param versions, (W^T, Wout^T)): mix_features
 
     def graph_for(self, x, edge):
         key = (_tensor_key(edge), int(x.shape[1]))
@@ -155,21 +254,41 @@ class SpGraphAttentionLayer(nn.Module):
                                   ops.gat_workspace(x, B)))
         return self._folded[1]
 
+    def transposed(self):
+        """(W^T [att, C], Wout^T [C, att]) contiguous, cached per parameter version: the
+        [Nout, K] operands of the two products of mix_features (stable buffers, so
+        captured step graphs keep replaying)."""
+        key = (_tensor_key(self.W), _tensor_key(self.Wout))
+        if self._transposed is None or self._transposed[0] != key:
+            self._transposed = (key, (self.W.detach().t().contiguous(), self.Wout.detach().t().contiguous()))
+        return self._transposed[1]
+
+    def project(self, x):
+        """wx = x W (:123) [.., attention_dim] fp32 (mix_features)."""
+        if x.dtype != torch.float32:
+            raise NotImplementedError("gnpde: GAT mix_features runs on fp32 states only (got %s)" % x.dtype)
+        Wt, _ = self.transposed()
+        if _needs_grad(x, self.W):
+            return _GatProject.apply(x, self.W, Wt)
+        return ops.linear(x, Wt)[0].view(tuple(x.shape[:-1]) + (self.attention_dim,))
+
     def node_scores(self, g, x):
         """NodeScores of mode SCORE_GAT for this RHS evaluation (x fp32)."""
         W, a, ws = self.folded(x, g.B)
         return ops.gat_scores(g, x, W, a, self.h, self.alpha, ws=ws)
 
     def forward(self, x, edge, y=None):
-        """Returns (attention [B,E,h], None): the per-edge softmax attention of :135
-        in COO order.  ``wx`` (:123) is not materialised (dead for mix_features=False)."""
+        """Returns (attention [B,E,h], wx): the per-edge softmax attention of :135 in COO
+        order, and wx = x W (:123) under mix_features — None otherwise (dead there, not
+        materialised)."""
         g = self.graph_for(x, edge)
         norm_idx = int(self.opt['attention_norm_idx'])
+        wx = self.project(x) if self.mix else None
         if _needs_grad(x, self.W, self.a):
-            return _GatEdgeAttention.apply(x, self.W, self.a, self, g, norm_idx), None
+            return _GatEdgeAttention.apply(x, self.W, self.a, self, g, norm_idx), wx
         ns = self.node_scores(g, x.float())
         m, rl = ops.softmax_stats(g, ns, norm_idx)
-        return ops.edge_attention(g, ns, m, rl, norm_idx), None
+        return ops.edge_attention(g, ns, m, rl, norm_idx), wx
 
     def __repr__(self):
         return self.__class__.__name__ + ' (' + str(self.in_features) + ' -> ' + str(self.out_features) + ')'
@@ -191,10 +310,17 @@ class ODEFuncAtt(ODEFunc):
         self.y = None
 
     def multiply_attention(self, x, attention, wx=None):
-        """A_mean x with attention [B,E,h] given explicitly (:40-47)."""
+        """A_mean x with attention [B,E,h] given explicitly (:40-47); under mix_features
+        (A_mean wx) Wout (:29-38), wx = x W when not given."""
         g = self.graph_for(x)
         w = g.gather_weights(attention.detach().float())
-        return ops.spmm_rhs(g, w, x, rhs=False)
+        lay = self.multihead_att_layer
+        if not lay.mix:
+            return ops.spmm_rhs(g, w, x, rhs=False)
+        if wx is None:
+            wx = lay.project(x)
+        z = ops.spmm_rhs(g, w, wx.detach().float().view(g.B, g.N, lay.attention_dim), rhs=False)
+        return ops.linear_rhs(z, lay.transposed()[1], x.detach(), rhs=False)
 
     def rhs_stage(self, t, x, stage):
         """forward(t, x) with the solver's stage combination fused into the
@@ -206,7 +332,10 @@ class ODEFuncAtt(ODEFunc):
         device CSR / CSC + plans, the layer's cached operands (W, a and the scratch
         U is folded into) and, with add_source, the stable x0 buffer."""
         g = self.graph_for(x)
-        st = [g, self.multihead_att_layer.folded(x, g.B)]
+        lay = self.multihead_att_layer
+        st = [g, lay.folded(x, g.B)]
+        if lay.mix:
+            st.append(lay.transposed())
         if self.opt.get('add_source', False):
             st.append(self.stable_x0(x))
         return st
@@ -228,7 +357,10 @@ class ODEFuncAtt(ODEFunc):
         self.nfe += 1
         g = self.graph_for(x)
         lay = self.multihead_att_layer
-        if stage is None and _needs_grad(x, self.alpha_train, self.beta_train, lay.W, lay.a):
+        if lay.mix and x.dtype != torch.float32:
+            raise NotImplementedError("gnpde: GAT mix_features runs on fp32 states only (got %s)" % x.dtype)
+        if stage is None and _needs_grad(x, self.alpha_train, self.beta_train, lay.W, lay.a,
+                                         lay.Wout if lay.mix else None):
             return self._rhs_autograd(g, x)
         norm_idx = int(self.opt['attention_norm_idx'])
         add_source = bool(self.opt.get('add_source', False))
@@ -243,6 +375,15 @@ class ODEFuncAtt(ODEFunc):
                   stage=stage)
         # a bf16 state: scores from an fp32 copy, the weights pass and the bf16 K1 (ops.attn_rhs)
         ns = lay.node_scores(g, x.float() if x.dtype == torch.bfloat16 else x)
+        if lay.mix:
+            # the value projection: z = A_mean (x W) by the GAT-weight K1 at width attention_dim
+            # (no epilogue), then z Wout with the RHS / stage epilogue fused (ops.linear_rhs)
+            Wt, Wot = lay.transposed()
+            wx = ops.linear(x, Wt)[0].view(g.B, g.N, lay.attention_dim)
+            z = ops.attn_rhs(g, ns, None, None, norm_idx, wx, rhs=False, fuse=ops.gat_fuse_default(lay.h, norm_idx))
+            # a solver stage takes f + the stage pass: the same bits as the kernel's fused stage, and
+            # faster on the benchmark graph (0.195-0.211 against 0.212-0.217 ms)
+            return ops.linear_rhs(z, Wot, x, fuse=False, **kw)
         # the fused K1 where it measured faster than the weights pass + K1 (ops.gat_fuse_default)
         return ops.attn_rhs(g, ns, None, None, norm_idx, x, fuse=ops.gat_fuse_default(lay.h, norm_idx), **kw)
 
@@ -259,6 +400,11 @@ class ODEFuncAtt(ODEFunc):
         if x0 is not None and x0.dtype != torch.float32:
             x0 = x0.float()
         ad = att.detach()
+        lay = self.multihead_att_layer
+        if lay.mix:  # + Wout, and W through the value path as well (_GatMixRHS)
+            Wt, Wot = lay.transposed()
+            return _GatMixRHS.apply(x, self.alpha_train, self.beta_train, att, lay.W, lay.Wout, g, Wt, Wot, x0,
+                                    not self.opt.get('no_alpha_sigmoid', False), add_source)
         return _LaplacianRHS.apply(x, self.alpha_train, self.beta_train, att, g, g.gather_weights(ad),
                                    lambda: g.gather_weights(ad, transpose=True), x0,
                                    not self.opt.get('no_alpha_sigmoid', False), add_source)

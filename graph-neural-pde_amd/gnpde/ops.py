@@ -1073,6 +1073,67 @@ def linear_wgrad(gy, x):
     return out
 
 
+def _linear_rhs_fuses(stage):
+    """Whether gnpde_linear_rhs_f32 fuses ``stage``: the fixed-grid epilogue (f_out, outputs,
+    at most STAGE_PRE_K operands); everything else takes f + stage_apply."""
+    return not (stage.wide or stage.dot is not None or stage.dense is not None or stage.scale_rows is not None
+                or stage.out_rows is not None or stage.scale is not None or stage.f_lin != 0.0)
+
+
+def linear_rhs(z, Wt, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoid=True, add_source=False, out=None,
+               stage=None, fuse=True):
+    """f = a*(z Wt^T - x) [+ b*x0] (or z Wt^T with rhs=False): the output product of the
+    GAT value projection with the RHS epilogue and the fixed-grid stage combination fused
+    (gnpde_linear_rhs_f32).  z [..., K] fp32, Wt [C, K] fp32 (= Wout^T), x / x0 [..., C]
+    fp32 with the rows of z.  stage: a ``Stage`` -> its outputs are written instead of f
+    (returns None); a stage the kernel does not fuse (Stage.wide, a coefficient scale,
+    out_rows, f_lin), or any stage with fuse=False, takes f first and the stage in a second
+    pass (stage_apply), as spmm_rhs does for on-the-fly weights — the same bits."""
+    if stage is not None and not (fuse and _linear_rhs_fuses(stage)):
+        f = linear_rhs(z, Wt, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
+                       add_source=add_source)
+        stage_apply(stage, f, x, x)
+        return None
+    zr = _rows(z, "z")
+    _require_gpu(Wt, "Wt", torch.float32)
+    Wt = Wt.contiguous()
+    C, K = Wt.shape
+    if zr.shape[1] != K:
+        raise ValueError("linear_rhs: z has %d columns, Wt expects %d" % (zr.shape[1], K))
+    R = zr.shape[0]
+    dev = zr.device
+    if x is None and (rhs or stage is not None):
+        raise ValueError("linear_rhs: x required")
+    xr = _rows(x, "x") if x is not None else None
+    if xr is not None and tuple(xr.shape) != (R, C):
+        raise ValueError("linear_rhs: x is %s, z Wt^T is (%d, %d)" % (tuple(xr.shape), R, C))
+    a = _scalar(alpha, "alpha", dev) if rhs else None
+    if rhs and a is None:
+        raise ValueError("linear_rhs: alpha required")
+    b = _scalar(beta, "beta", dev) if add_source else None
+    x0r = _rows(x0, "x0") if add_source else None
+    if x0r is not None and tuple(x0r.shape) != (R, C):
+        raise ValueError("linear_rhs: x0 is %s, z Wt^T is (%d, %d)" % (tuple(x0r.shape), R, C))
+    st = None
+    if stage is not None:
+        for t in stage.tensors():
+            _require_gpu(t, "stage tensor", torch.float32)
+            if not t.is_contiguous() or t.numel() != R * C:
+                raise ValueError("stage tensors must be contiguous and shaped like x")
+        st = ctypes.byref(stage.struct(xr))
+    elif out is None:
+        out = torch.empty(R, C, dtype=torch.float32, device=dev)
+    else:
+        _require_gpu(out, "out", torch.float32)
+        if not out.is_contiguous() or out.numel() != R * C:
+            raise ValueError("linear_rhs: out must be contiguous and hold %d x %d" % (R, C))
+    _lib.call("gnpde_linear_rhs_f32", _ptr(zr), R, K, K, _ptr(Wt), C, _ptr(xr), C, _ptr(x0r), C, _ptr(a), _ptr(b),
+              _flags(rhs, alpha_sigmoid, add_source), _ptr(out), C, st, _stream(dev))
+    if stage is not None:
+        return None
+    return out.view(x.shape if x is not None else tuple(z.shape[:-1]) + (C,))
+
+
 class NodeScores(object):
     """Per-RHS node-level operands of the attention scores.  GAT (SCORE_GAT): ``sp``
     = the node-score pairs [R, 2h] fp64 = [sl | sr] and ``slope`` the LeakyReLU slope;

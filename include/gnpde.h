@@ -445,6 +445,31 @@ int gnpde_linear_bf16(const void* x, int64_t R, int64_t K, int64_t ldx, const fl
                       int64_t Nout, int64_t split, float* out_a, int64_t lda, float* out_b, int64_t ldb,
                       void* stream);
 
+/* The output product of the GAT value projection fused with the RHS epilogue and
+ * the fixed-grid stage combination (mix_features, function_GAT_attention.py:38 and
+ * :60-68; an entry point added under ABI 8, no struct changed):
+ *   ax[r,:] = sum_k z[r,k] * Wt[:,k]      z [R, ldz] fp32, Wt [C, K] row-major = Wout^T
+ *   f[r,:]  = ax                                  (flags & 1 == 0; x may be NULL)
+ *           = a*(ax - x[r,:]) [+ b*x0[r,:]]        (GNPDE_EPI_RHS)
+ * flags, the sigmoid and the device scalars alpha / beta exactly as in
+ * gnpde_spmm_rhs_f32.  stage: NULL -> f is stored; otherwise the fixed-grid stage
+ * epilogue decides what is stored (f is ignored): f_out, n_out <= GNPDE_STAGE_MAX_OUT
+ * outputs, at most two shared operands, the aliasing rule above; no output (nor f)
+ * may be z or the RHS input x.  err_rows, dot_rows, dense_*, scale_rows, f_lin,
+ * out_rows, coef_scale or more than two operands: GNPDE_EUNSUPPORTED (the caller
+ * stores f and applies the stage with gnpde_stage_apply_f32).  The stage arithmetic
+ * is the one K1 and gnpde_stage_apply_f32 run per element, so the fused stage equals
+ * f followed by gnpde_stage_apply_f32 bit for bit.  No atomics: repeated launches
+ * give the same bits.  K % 16 == 0, K <= 128, C % 4 == 0 and 16-byte aligned rows:
+ * the split-bf16 product of gnpde_linear_f32 on v_mfma_f32_32x32x16_bf16 (f32-GEMM
+ * accuracy); any other K >= 1, C >= 1: one exact-f32 fma chain per output.      */
+int gnpde_linear_rhs_f32(const float* z, int64_t R, int64_t K, int64_t ldz,
+                         const float* Wt /* [C, K] row-major = Wout^T */, int64_t C,
+                         const float* x, int64_t ldx, const float* x0, int64_t ldx0,
+                         const float* alpha, const float* beta, int flags,
+                         float* f, int64_t ldf,
+                         const gnpde_stage_epilogue_t* stage, void* stream);
+
 /* Weight gradient of the projection: gW[m, k] = sum_r gy[r, m] * x[r, k]
  * (gy [R, M] ld ldg = dL/d[q | k], x [R, K] ld ldx; gW [M, K] ld ldw), the
  * backward of nn.Linear's weight for the Q / K of
