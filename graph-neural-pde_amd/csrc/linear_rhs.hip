@@ -40,9 +40,12 @@ constexpr int kLrhsTiles = 2;
 // every stage operand row of a (half) accumulator tile before combining any run
 // (wide_combine taking pre-read rows by slot): 170-226 VGPRs, the fused rk4 stage on
 // G-arxiv at 0.219-0.239 ms, unchanged from 0.213-0.244 ms.
-template <int KS, int STG>
+// BIAS: ax = z Wt^T + bias[C] ahead of the epilogue (gnpde_linear_rhs_bias_f32: the transformer
+// layer's Wout, an nn.Linear with a bias); the BIAS = false instantiation never reads `bias`.
+template <int KS, int STG, bool BIAS>
 __global__ __launch_bounds__(256, 2) void linear_rhs_split_kernel(const float* __restrict__ z, int R, int64_t ldz,
-                                                                   const float* __restrict__ Wt, int C, Epi e) {
+                                                                   const float* __restrict__ Wt, int C, Epi e,
+                                                                   const float* __restrict__ bias) {
   constexpr int K = 16 * KS, KH = 8 * KS;
   extern __shared__ __attribute__((aligned(16))) bf16x8_t wfrag[];  // [tile][piece 3][step KS][lane 64]
   constexpr int NT = kLrhsTiles;
@@ -130,6 +133,18 @@ __global__ __launch_bounds__(256, 2) void linear_rhs_split_kernel(const float* _
       const int n0 = col0 + 32 * t;  // wave-uniform
       if (n0 >= C) break;
       EpiPre<4, float, STG> p[4];
+      if constexpr (BIAS) {  // the lane's four runs of this tile: columns n0 + 8g + 4h .. + 3
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int c = n0 + 8 * g + 4 * h;
+          float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (c < C) bv = *reinterpret_cast<const float4*>(bias + c);  // C % 4 == 0: a whole run
+          acc[t][4 * g] += bv.x;
+          acc[t][4 * g + 1] += bv.y;
+          acc[t][4 * g + 2] += bv.z;
+          acc[t][4 * g + 3] += bv.w;
+        }
+      }
       if (tile * kLinRowsPerWave + kLinRowsPerWave <= R && n0 + 32 <= C) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) epi_prefetch<4, STG, float>(e, row, n0 + 8 * g + 4 * h, p[g]);
@@ -157,10 +172,10 @@ __global__ __launch_bounds__(256, 2) void linear_rhs_split_kernel(const float* _
 
 // Any K >= 1, C >= 1: one thread per output element, an exact-f32 fma chain over k
 // ascending.
-template <int STG>
+template <int STG, bool BIAS>
 __global__ __launch_bounds__(256) void linear_rhs_plain_kernel(const float* __restrict__ z, int64_t R, int K,
                                                                 int64_t ldz, const float* __restrict__ Wt, int C,
-                                                                Epi e) {
+                                                                Epi e, const float* __restrict__ bias) {
   const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (idx >= R * C) return;
   const int64_t row = idx / C;
@@ -169,6 +184,7 @@ __global__ __launch_bounds__(256) void linear_rhs_plain_kernel(const float* __re
   const float* __restrict__ wr = Wt + (int64_t)c * K;
   float ax[1] = {0.f};
   for (int k = 0; k < K; ++k) ax[0] = fmaf(zr[k], wr[k], ax[0]);
+  if constexpr (BIAS) ax[0] += bias[c];
   const bool need_x = (e.flags & GNPDE_EPI_RHS) != 0;
   const float a = need_x ? epi_alpha(e) : 0.f;
   const float b = (e.flags & GNPDE_ADD_SOURCE) ? *e.beta : 0.f;
@@ -179,10 +195,11 @@ __global__ __launch_bounds__(256) void linear_rhs_plain_kernel(const float* __re
 
 using namespace gnpde;
 
-extern "C" int gnpde_linear_rhs_f32(const float* z, int64_t R, int64_t K, int64_t ldz, const float* Wt, int64_t C,
-                                    const float* x, int64_t ldx, const float* x0, int64_t ldx0, const float* alpha,
-                                    const float* beta, int flags, float* f, int64_t ldf,
-                                    const gnpde_stage_epilogue_t* stage, void* stream) {
+template <bool BIAS>
+static int linear_rhs_impl(const float* z, int64_t R, int64_t K, int64_t ldz, const float* Wt, int64_t C,
+                           const float* bias, const float* x, int64_t ldx, const float* x0, int64_t ldx0,
+                           const float* alpha, const float* beta, int flags, float* f, int64_t ldf,
+                           const gnpde_stage_epilogue_t* stage, void* stream) {
   GNPDE_REQUIRE(z && Wt, GNPDE_EINVAL, "linear_rhs: NULL pointer");
   GNPDE_REQUIRE(R >= 0 && R < INT32_MAX && K >= 1 && K < INT32_MAX && ldz >= K && C >= 1 && C < INT32_MAX,
                 GNPDE_EINVAL, "linear_rhs: bad sizes");
@@ -215,6 +232,7 @@ extern "C" int gnpde_linear_rhs_f32(const float* z, int64_t R, int64_t K, int64_
 
   auto row16 = [](const void* p, int64_t ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); };
   bool fast = K % 16 == 0 && K <= 128 && C % 4 == 0 && row16(z, ldz) && aligned16(Wt) && row16(f, ldf) && ldf % 4 == 0;
+  if (BIAS) fast = fast && aligned16(bias);
   if (rhs) fast = fast && row16(x, ldx);
   if (flags & GNPDE_ADD_SOURCE) fast = fast && row16(x0, ldx0);
   if (stage) {
@@ -231,12 +249,12 @@ extern "C" int gnpde_linear_rhs_f32(const float* z, int64_t R, int64_t K, int64_
     const int64_t blocks = ceil_div(ceil_div(ntiles, per_wave), kWavesPerBlock);
     const dim3 gt((unsigned)blocks, (unsigned)slices);
     const size_t lds = sizeof(bf16x8_t) * (size_t)kLrhsTiles * 3 * (size_t)(K / 16) * kWave;
-#define GNPDE_LRHS_K(KS)                                                                   \
-  do {                                                                                     \
-    if (stage)                                                                             \
-      linear_rhs_split_kernel<KS, 2><<<gt, kBlock, lds, s>>>(z, (int)R, ldz, Wt, (int)C, e); \
-    else                                                                                   \
-      linear_rhs_split_kernel<KS, 0><<<gt, kBlock, lds, s>>>(z, (int)R, ldz, Wt, (int)C, e); \
+#define GNPDE_LRHS_K(KS)                                                                                \
+  do {                                                                                                  \
+    if (stage)                                                                                          \
+      linear_rhs_split_kernel<KS, 2, BIAS><<<gt, kBlock, lds, s>>>(z, (int)R, ldz, Wt, (int)C, e, bias); \
+    else                                                                                                \
+      linear_rhs_split_kernel<KS, 0, BIAS><<<gt, kBlock, lds, s>>>(z, (int)R, ldz, Wt, (int)C, e, bias); \
   } while (0)
     switch (K / 16) {
       case 1: GNPDE_LRHS_K(1); break;
@@ -256,9 +274,28 @@ extern "C" int gnpde_linear_rhs_f32(const float* z, int64_t R, int64_t K, int64_
   GNPDE_REQUIRE(nblk < INT32_MAX, GNPDE_EUNSUPPORTED, "linear_rhs: %lld x %lld outputs exceed the plain kernel's grid",
                 (long long)R, (long long)C);
   if (stage)
-    linear_rhs_plain_kernel<2><<<(unsigned)nblk, kBlock, 0, s>>>(z, R, (int)K, ldz, Wt, (int)C, e);
+    linear_rhs_plain_kernel<2, BIAS><<<(unsigned)nblk, kBlock, 0, s>>>(z, R, (int)K, ldz, Wt, (int)C, e, bias);
   else
-    linear_rhs_plain_kernel<0><<<(unsigned)nblk, kBlock, 0, s>>>(z, R, (int)K, ldz, Wt, (int)C, e);
+    linear_rhs_plain_kernel<0, BIAS><<<(unsigned)nblk, kBlock, 0, s>>>(z, R, (int)K, ldz, Wt, (int)C, e, bias);
   GNPDE_LAUNCH_CHECK();
   return GNPDE_OK;
+}
+
+extern "C" int gnpde_linear_rhs_f32(const float* z, int64_t R, int64_t K, int64_t ldz, const float* Wt, int64_t C,
+                                    const float* x, int64_t ldx, const float* x0, int64_t ldx0, const float* alpha,
+                                    const float* beta, int flags, float* f, int64_t ldf,
+                                    const gnpde_stage_epilogue_t* stage, void* stream) {
+  return linear_rhs_impl<false>(z, R, K, ldz, Wt, C, nullptr, x, ldx, x0, ldx0, alpha, beta, flags, f, ldf, stage,
+                                stream);
+}
+
+// ax = z Wt^T + bias (the transformer layer's Wout, function_transformer_attention.py:31); bias NULL: the entry above
+extern "C" int gnpde_linear_rhs_bias_f32(const float* z, int64_t R, int64_t K, int64_t ldz, const float* Wt,
+                                         int64_t C, const float* bias, const float* x, int64_t ldx, const float* x0,
+                                         int64_t ldx0, const float* alpha, const float* beta, int flags, float* f,
+                                         int64_t ldf, const gnpde_stage_epilogue_t* stage, void* stream) {
+  if (!bias)
+    return linear_rhs_impl<false>(z, R, K, ldz, Wt, C, nullptr, x, ldx, x0, ldx0, alpha, beta, flags, f, ldf, stage,
+                                  stream);
+  return linear_rhs_impl<true>(z, R, K, ldz, Wt, C, bias, x, ldx, x0, ldx0, alpha, beta, flags, f, ldf, stage, stream);
 }

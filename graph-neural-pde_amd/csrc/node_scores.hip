@@ -104,7 +104,8 @@ __global__ __launch_bounds__(256) void attn_weights_kernel(const int* __restrict
   }
 }
 
-// att[perm[p]*H + h] = exp(s_p,h - m[g,h]) * rl[g,h]   (COO order, per head)
+// att[perm[p]*H + h] = exp(s_p,h - m[g,h]) * rl[g,h]   (COO order, per head; perm NULL: att[p*H + h],
+// aggregation-CSR order — the per-head weights of gnpde_head_aggregate_f32)
 __global__ __launch_bounds__(256) void edge_attention_kernel(const int* __restrict__ rowidx,
                                                               const int* __restrict__ col,
                                                               const int* __restrict__ perm, int64_t nnz,
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(256) void edge_attention_kernel(const int* __restri
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * blockDim.x) {
     const int r = rowidx[p], c = col[p];
     const int64_t g = norm_idx == 0 ? r : c;
-    const int64_t e = perm[p];
+    const int64_t e = perm ? perm[p] : p;
     for (int h = 0; h < H; ++h) {
       const double s = sa.score(r, c, h);
       att[e * H + h] = expf((float)(s - m[g * H + h])) * rl[g * H + h];
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(256) void attn_team_kernel(const int* __restrict__ 
       const int64_t pm = p0 + min(t, cnt - 1);
       my_r = rowidx[pm];
       my_c = col[pm];
-      if (COO) my_dst = perm[pm];
+      if (COO) my_dst = perm ? perm[pm] : (int)pm;  // perm NULL: the CSR position itself
     }
     const int jmax = wave_max_int(cnt);
     for (int j = 0; j < jmax; j += kTeamEdges) {
@@ -1028,15 +1029,16 @@ int gnpde_attn_weights_f32(const int32_t* rowidx, const int32_t* col, int64_t nn
   return GNPDE_OK;
 }
 
-int gnpde_edge_attention_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
-                             int norm_idx, int mode, int64_t heads, int64_t dk, const double* cs, const float* q,
-                             const float* k, int64_t ldqk, float score_p0, float score_p1, const double* m,
-                             const float* rl, float* att, void* stream) {
+// perm NULL: the CSR-order output of gnpde_edge_attention_csr_f32
+static int edge_attention_impl(const int32_t* rowidx, const int32_t* col, const int32_t* perm, bool coo, int64_t nnz,
+                               int norm_idx, int mode, int64_t heads, int64_t dk, const double* cs, const float* q,
+                               const float* k, int64_t ldqk, float score_p0, float score_p1, const double* m,
+                               const float* rl, float* att, void* stream) {
   int rc = check_score_args(mode, heads, dk, cs, q, k);
   if (rc) return rc;
   GNPDE_REQUIRE(norm_idx == 0 || norm_idx == 1, GNPDE_EINVAL, "edge_attention: norm_idx must be 0 or 1");
   if (nnz == 0) return GNPDE_OK;
-  GNPDE_REQUIRE(rowidx && col && perm && m && rl && att, GNPDE_EINVAL, "edge_attention: NULL pointer");
+  GNPDE_REQUIRE(rowidx && col && (perm || !coo) && m && rl && att, GNPDE_EINVAL, "edge_attention: NULL pointer");
   const ScoreArgs sa = make_score_args(mode, heads, dk, cs, q, k, ldqk, score_p0, score_p1);
   Team tm = team_geometry(sa);
   if ((uint64_t)nnz * heads * 4 >= kBufRecords) tm.T = 0;  // buffer-store offsets are 32-bit
@@ -1048,6 +1050,22 @@ int gnpde_edge_attention_f32(const int32_t* rowidx, const int32_t* col, const in
                                                                             rl, att);
   GNPDE_LAUNCH_CHECK();
   return GNPDE_OK;
+}
+
+int gnpde_edge_attention_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
+                             int norm_idx, int mode, int64_t heads, int64_t dk, const double* cs, const float* q,
+                             const float* k, int64_t ldqk, float score_p0, float score_p1, const double* m,
+                             const float* rl, float* att, void* stream) {
+  return edge_attention_impl(rowidx, col, perm, true, nnz, norm_idx, mode, heads, dk, cs, q, k, ldqk, score_p0,
+                             score_p1, m, rl, att, stream);
+}
+
+int gnpde_edge_attention_csr_f32(const int32_t* rowidx, const int32_t* col, int64_t nnz, int norm_idx, int mode,
+                                 int64_t heads, int64_t dk, const double* cs, const float* q, const float* k,
+                                 int64_t ldqk, float score_p0, float score_p1, const double* m, const float* rl,
+                                 float* att, void* stream) {
+  return edge_attention_impl(rowidx, col, nullptr, false, nnz, norm_idx, mode, heads, dk, cs, q, k, ldqk, score_p0,
+                             score_p1, m, rl, att, stream);
 }
 
 size_t gnpde_keysum_workspace_bytes(int64_t B, int64_t N, int64_t C, int64_t att) {

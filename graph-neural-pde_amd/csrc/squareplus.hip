@@ -276,7 +276,8 @@ __global__ __launch_bounds__(256) void squareplus_hub_kernel(const int4* __restr
 }
 
 // Edge-parallel over the aggregation CSR (rowidx = source, col = destination, perm -> COO):
-// att[e,h] = p * rl[g,h] (COO) and / or the head-mean weight w[p] (CSR order).
+// att[e,h] = p * rl[g,h] (COO; att_csr: att[p,h], CSR order — the per-head weights of
+// gnpde_head_aggregate_f32) and / or the head-mean weight w[p] (CSR order).
 template <bool NODE>
 __global__ __launch_bounds__(256) void squareplus_edge_kernel(const int* __restrict__ rowidx,
                                                                const int* __restrict__ col,
@@ -285,7 +286,7 @@ __global__ __launch_bounds__(256) void squareplus_edge_kernel(const int* __restr
                                                                const float* __restrict__ sc,
                                                                const double* __restrict__ M,
                                                                const float* __restrict__ rl, float* __restrict__ w_out,
-                                                               float* __restrict__ att) {
+                                                               float* __restrict__ att, int att_csr) {
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * blockDim.x) {
     const int r = rowidx[p], c = col[p];
     const int64_t e = perm[p];
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(256) void squareplus_edge_kernel(const int* __restr
     for (int h = 0; h < H; ++h) {
       const float pv = NODE ? pn[(int64_t)r * H + h] : squareplus_p(sc[e * H + h] - Mb);
       const float rg = rl[g * H + h];
-      if (att) att[e * H + h] = pv * rg;
+      if (att) att[(att_csr ? p : e) * H + h] = pv * rg;
       acc = squareplus_mean_step(pv, rg, acc);
     }
     if (w_out) w_out[p] = acc / (float)H;
@@ -459,7 +460,8 @@ int gnpde_squareplus_stats_f32(const int32_t* items, int64_t n_items, const int3
 
 static int squareplus_edges(const char* what, const int32_t* rowidx, const int32_t* col, const int32_t* perm,
                             int64_t nnz, int64_t N, int norm_idx, int mode, int64_t heads, const float* pn,
-                            const float* sc, const double* M, const float* rl, float* w_out, float* att, void* stream) {
+                            const float* sc, const double* M, const float* rl, float* w_out, float* att, void* stream,
+                            bool att_csr = false) {
   int rc = sp_mode_check(mode, what);
   if (rc) return rc;
   GNPDE_REQUIRE(heads >= 1 && heads <= 16, GNPDE_EUNSUPPORTED, "%s: heads=%lld not in [1,16]", what, (long long)heads);
@@ -472,10 +474,12 @@ static int squareplus_edges(const char* what, const int32_t* rowidx, const int32
   const unsigned grid = sp_grid(nnz, 16384);
   if (node)
     squareplus_edge_kernel<true><<<grid, kBlock, 0, as_stream(stream)>>>(rowidx, col, perm, nnz, N, norm_idx,
-                                                                         (int)heads, pn, sc, M, rl, w_out, att);
+                                                                         (int)heads, pn, sc, M, rl, w_out, att,
+                                                                         (int)att_csr);
   else
     squareplus_edge_kernel<false><<<grid, kBlock, 0, as_stream(stream)>>>(rowidx, col, perm, nnz, N, norm_idx,
-                                                                          (int)heads, pn, sc, M, rl, w_out, att);
+                                                                          (int)heads, pn, sc, M, rl, w_out, att,
+                                                                          (int)att_csr);
   GNPDE_LAUNCH_CHECK();
   return GNPDE_OK;
 }
@@ -492,6 +496,13 @@ int gnpde_squareplus_attention_f32(const int32_t* rowidx, const int32_t* col, co
                                    const double* M, const float* rl, float* att, void* stream) {
   return squareplus_edges("squareplus_attention", rowidx, col, perm, nnz, N, norm_idx, mode, heads, pn, sc, M, rl,
                           nullptr, att, stream);
+}
+
+int gnpde_squareplus_attention_csr_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
+                                       int64_t N, int norm_idx, int mode, int64_t heads, const float* pn,
+                                       const float* sc, const double* M, const float* rl, float* att, void* stream) {
+  return squareplus_edges("squareplus_attention_csr", rowidx, col, perm, nnz, N, norm_idx, mode, heads, pn, sc, M, rl,
+                          nullptr, att, stream, true);
 }
 
 int gnpde_attn_sp_rhs_f32(const int32_t* items, int64_t n_items, int32_t* heavy, int64_t n_heavy, const int32_t* col,

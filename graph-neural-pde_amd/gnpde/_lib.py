@@ -99,6 +99,12 @@ SIGNATURES = {
     "gnpde_linear_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "gnpde_linear_rhs_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64,
                                     ctypes.POINTER(StageEpilogue), _vp]),
+    "gnpde_linear_rhs_bias_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int,
+                                         _vp, _i64, ctypes.POINTER(StageEpilogue), _vp]),
+    "gnpde_head_aggregate_fast": (_int, [_i64, _i64]),
+    "gnpde_head_aggregate_workspace_floats": (_i64, [_i64, _i64]),
+    "gnpde_head_aggregate_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp,
+                                        _i64, _vp, _i64, _vp]),
     "gnpde_linear_wgrad_workspace_bytes": (_size, [_i64, _i64, _i64]),
     "gnpde_linear_wgrad_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _size, _vp]),
     "gnpde_keysum_workspace_bytes": (_size, [_i64, _i64, _i64, _i64]),
@@ -113,6 +119,8 @@ SIGNATURES = {
                                       _vp, _vp, _vp]),
     "gnpde_edge_attention_f32": (_int, [_vp, _vp, _vp, _i64, _int, _int, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _f32,
                                         _vp, _vp, _vp, _vp]),
+    "gnpde_edge_attention_csr_f32": (_int, [_vp, _vp, _i64, _int, _int, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _f32,
+                                            _vp, _vp, _vp, _vp]),
     "gnpde_seg_block_edges": (_int, [_int, _i64, _i64]),
     "gnpde_seg_plan_build": (_int, [_vp, _i64, ctypes.c_int32, _vp, _i64, _vp, _i64, _vp, _i64, c_i64p, c_i64p,
                                     c_i64p]),
@@ -151,6 +159,8 @@ SIGNATURES = {
                                             _vp]),
     "gnpde_squareplus_attention_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp,
                                               _vp]),
+    "gnpde_squareplus_attention_csr_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp]),
     "gnpde_attn_sp_rhs_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
                                      _int, _vp, _i64, _vp, _i64, ctypes.POINTER(StageEpilogue), _vp]),
     "gnpde_squareplus_backward_workspace_bytes": (_size, [_i64]),

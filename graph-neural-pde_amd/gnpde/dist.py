@@ -498,6 +498,15 @@ class _Comm(object):
         dist.all_gather_into_tensor(out, t, group=self.group)
 
 
+def _refuse_mix_features(mix_features, who):
+    """The sharded attention classes aggregate the state with head-mean weights; the
+    transformer layer's value projection (mix_features: per-head weights over V(x), then
+    Wout) is a single-GPU path."""
+    if mix_features:
+        raise NotImplementedError("%s: mix_features (the transformer value projection) is not sharded; run it on "
+                                  "one GPU (gnpde.ODEFuncTransformerAtt with opt['gnpde_mix_features'])" % who)
+
+
 def _refuse_square_plus(square_plus, who):
     """The sharded attention classes normalise with the edge softmax only: the squareplus
     shift is a maximum over ALL edges of a batch element (one more collective in front of
@@ -677,8 +686,10 @@ class ColumnShardedTransformer(object):
 
     def __init__(self, edge_index, num_nodes, C, Wq, bq, Wk, bk, heads, norm_idx, alpha, score_mode='reference',
                  beta=None, x0_local=None, add_source=False, alpha_sigmoid=True, group=None, local=None,
-                 chunk=None, comm=None, partition_stats=True, edge_weights=None, square_plus=False):
+                 chunk=None, comm=None, partition_stats=True, edge_weights=None, square_plus=False,
+                 mix_features=False):
         _refuse_square_plus(square_plus, "ColumnShardedTransformer")
+        _refuse_mix_features(mix_features, "ColumnShardedTransformer")
         self.group = group
         self.comm = comm if comm is not None else _Comm(group)
         self.rank = dist.get_rank(group)
@@ -947,8 +958,10 @@ class RowShardedTransformer(object):
 
     def __init__(self, edge_index, num_nodes, C, Wq, bq, Wk, bk, heads, norm_idx, alpha, score_mode='reference',
                  beta=None, x0_local=None, add_source=False, alpha_sigmoid=True, group=None,
-                 chunk=None, row_weight=ROW_WEIGHT, comm=None, local=None, partition_stats=True, square_plus=False):
+                 chunk=None, row_weight=ROW_WEIGHT, comm=None, local=None, partition_stats=True, square_plus=False,
+                 mix_features=False):
         _refuse_square_plus(square_plus, "RowShardedTransformer")
+        _refuse_mix_features(mix_features, "RowShardedTransformer")
         if edge_index.shape[0] != 1:
             raise NotImplementedError("RowShardedTransformer: one graph (B = 1); shard batches with shard_batch")
         if int(norm_idx) not in (0, 1) or score_mode not in ('reference', 'per_edge'):

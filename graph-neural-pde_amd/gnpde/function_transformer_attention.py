@@ -36,9 +36,24 @@ cached on the layer (``squareplus_buffers``); nothing is read on the host.  The
 uniform case keeps its cached 1/outdeg weights.  DESIGN.md §6.12.
 
 V and Wout are dead when ``mix_features=False`` (:33-41) and are never
-computed; the parameters exist for state_dict compatibility.  Settings the
-fork cannot execute (``mix_features`` :23-31, ``square_plus`` :264 without
-``gnpde_square_plus``, ``multi_modal`` :171/222, beltrami+exp_kernel :164-167)
+computed there; the parameters exist for state_dict compatibility.
+``mix_features=True`` (the value projection, :23-32) runs when the option dict also sets
+``opt['gnpde_mix_features'] = True``: the reference's call site hands
+``multiply_attention`` the tuple ``(v, prods)`` (:50), so the option cannot run there, and
+the key selects what its pieces compute when composed as intended
+(``multiply_attention(x, attention, values[0])``):
+  v = V(x) [B,N,att], head h owning columns h*dk .. h*dk+dk-1
+  z[b,i,:] = (1/h) sum_{e: row(e) = i} sum_h att[b,e,h] v[b, col(e), h*dk : (h+1)*dk]   [B,N,dk]
+  ax = Wout(z),  f = alpha (ax - x) [+ beta x0]
+One RHS is then: the node scores and statistics as above, the per-head attention in
+aggregation-CSR order [nnz, h] (the attention pass that serves every score mode, grouping
+and normaliser, with a CSR-order output; cached for the uniform case), v on the matrix
+cores (gnpde_linear_f32), the per-head aggregation (gnpde_head_aggregate_f32,
+csrc/head_aggregate.hip: K1's plan items, per-head weights, the heads reduced across
+lanes) and Wout with its bias and the RHS / stage epilogue fused
+(gnpde_linear_rhs_bias_f32).  fp32 states, one GPU, the user's node numbering.
+DESIGN.md §6.16.  Settings the fork cannot execute (``mix_features`` without
+``gnpde_mix_features``, ``square_plus`` :264 without ``gnpde_square_plus``, ``multi_modal`` :171/222, beltrami+exp_kernel :164-167)
 raise NotImplementedError.  ``reweight_attention`` is a no-op in the fork (the
 layer's ``edge_weights`` is captured as None at construction, :15 / :261) and
 is a no-op here.
@@ -71,9 +86,11 @@ from .utils import MaxNFEException
 
 
 def _check_supported(opt):
-    if opt.get('mix_features', False):
+    if opt.get('mix_features', False) and not opt.get('gnpde_mix_features', False):
         raise NotImplementedError("gnpde: mix_features=True is broken in the reference "
-                                  "(function_transformer_attention.py:29-31 uses a tuple as a tensor)")
+                                  "(function_transformer_attention.py:29-31 uses a tuple as a tensor); set "
+                                  "opt['gnpde_mix_features'] = True to run the intended call, "
+                                  "multiply_attention(x, attention, values[0])")
     if opt.get('square_plus', False) and not opt.get('gnpde_square_plus', False):
         raise NotImplementedError("gnpde: square_plus is broken in the reference (utils.squareplus called "
                                   "with a 2-D slice and without num_nodes, :264); set opt['gnpde_square_plus'] = "
@@ -131,6 +148,100 @@ class _EdgeAttention(torch.autograd.Function):
                 (so, do), (sl, dl) = ctx.p_shapes
                 g_ov, g_ls = gp[0].reshape(so).to(do), gp[1].reshape(sl).to(dl)
         return grads + (g_ov, g_ls, None, None, None)
+
+
+class _MixProject(torch.autograd.Function):
+    """v = V(x) (:226) on the matrix cores, with its backward (mix_features)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b):
+        ctx.save_for_backward(x, W)
+        return ops.linear(x.detach(), W.detach(), b.detach())[0].view(tuple(x.shape[:-1]) + (W.shape[0],))
+
+    @staticmethod
+    def backward(ctx, g_v):
+        x, W = ctx.saved_tensors
+        g_v = g_v.contiguous()
+        gx = ops.linear(g_v, W.detach().t().contiguous())[0].view(x.shape) if ctx.needs_input_grad[0] else None
+        gW = ops.linear_wgrad(g_v, x.detach()).to(W.dtype) if ctx.needs_input_grad[1] else None
+        gb = g_v.reshape(-1, g_v.shape[-1]).sum(0).to(W.dtype) if ctx.needs_input_grad[2] else None
+        return gx, gW, gb
+
+
+class _MixRHS(torch.autograd.Function):
+    """f = a (Wout(z) - x) [+ b x0], z = the per-head aggregation of v = V(x) with the
+    attention [B,E,h], as a function of (x, alpha, beta, attention, V, Wout): the forward
+    kernels of the no-grad path and a backward of existing passes, one launch per head
+    where the head slices differ.  With g = dL/df and gh = a g:
+      g_Wout = gh^T z, g_bout = sum_r gh, g_z = gh Wout,
+      g_att[e,h] = <g_z[row(e)], v[col(e), head h]> / H            (an SDDMM per head),
+      g_v[:, head h] = A_h^T g_z / H                               (K1 over the CSC per head),
+      g_V = g_v^T x, g_bv = sum_r g_v, g_x = -gh + g_v V,
+      g_alpha, g_beta by fp64 dots (as the Laplacian RHS)."""
+
+    @staticmethod
+    def forward(ctx, x, alpha_train, beta_train, att, Wv, bv, Wo, bo, g, x0, alpha_sigmoid, add_source):
+        xd, ad = x.detach(), att.detach().float().contiguous()
+        v = ops.linear(xd, Wv.detach(), bv.detach())[0]                        # [R, att]
+        z = ops.head_aggregate(g, ad, v, coo=True)                             # [R, dk]
+        f = ops.linear_rhs(z, Wo.detach(), xd, x0=x0, alpha=alpha_train.detach(), beta=beta_train.detach(), rhs=True,
+                           alpha_sigmoid=alpha_sigmoid, add_source=add_source, bias=bo.detach())
+        ctx.save_for_backward(x, alpha_train, beta_train, ad, Wv, Wo, bo, v, z)
+        ctx.g, ctx.x0 = g, x0
+        ctx.alpha_sigmoid, ctx.add_source = alpha_sigmoid, add_source
+        return f
+
+    @staticmethod
+    def backward(ctx, gf):
+        x, alpha_train, beta_train, ad, Wv, Wo, bo, v, z = ctx.saved_tensors
+        g = ctx.g
+        gf = gf.contiguous()
+        x, Wv, Wo, bo = x.detach(), Wv.detach(), Wo.detach(), bo.detach()
+        H = ad.shape[2]
+        dk = z.shape[1]
+        al = alpha_train.detach()
+        a = torch.sigmoid(al) if ctx.alpha_sigmoid else al
+        gh = (a.float() * gf).contiguous()
+        ghr = gh.reshape(g.R, -1)
+        need = ctx.needs_input_grad
+        gx = ga = gb = gatt = gWv = gbv = gWo = gbo = None
+        if need[6]:
+            gWo = ops.linear_wgrad(ghr, z).to(Wo.dtype)                        # [C, dk] = gh^T z
+        if need[7]:
+            gbo = ghr.sum(0).to(bo.dtype)
+        if need[0] or need[3] or need[4] or need[5]:
+            g_z = ops.linear(ghr, Wo.t().contiguous())[0]                      # [R, dk] = gh Wout
+            if need[3]:
+                gatt = torch.empty_like(ad)
+                for h in range(H):
+                    vh = v[:, h * dk:(h + 1) * dk].contiguous()
+                    gatt[:, :, h] = ops.sddmm(g, g_z, vh)
+                gatt = gatt / H
+            if need[0] or need[4] or need[5]:
+                g_v = torch.empty_like(v)
+                for h in range(H):
+                    g_v[:, h * dk:(h + 1) * dk] = ops.spmm_rhs(g, ops.gather_head(g.csc, ad, h, 1.0 / H), g_z,
+                                                               rhs=False, transpose=True)
+                if need[4]:
+                    gWv = ops.linear_wgrad(g_v, x.reshape(g.R, -1)).to(Wv.dtype)   # [att, C] = g_v^T x
+                if need[5]:
+                    gbv = g_v.sum(0).to(Wv.dtype)
+                if need[0]:
+                    gx = ops.linear(g_v, Wv.t().contiguous())[0].view(x.shape) - gh   # g_v V - gh
+        if need[1]:
+            one = torch.ones((), dtype=torch.float32, device=x.device)
+            d = ops.linear_rhs(z, Wo, x, alpha=one, rhs=True, alpha_sigmoid=False, bias=bo)   # ax - x
+            s = ops.dot(gf, d).to(alpha_train.dtype)  # fp64 accumulation, fixed order
+            if ctx.alpha_sigmoid:
+                sg = torch.sigmoid(al)
+                s = s * sg * (1 - sg)
+            ga = s.reshape(alpha_train.shape)
+        if need[2]:
+            if ctx.add_source:
+                gb = ops.dot(gf, ctx.x0.float()).to(beta_train.dtype).reshape(beta_train.shape)
+            else:
+                gb = torch.zeros_like(beta_train)
+        return gx, ga, gb, gatt, gWv, gbv, gWo, gbo, None, None, None, None
 
 
 def _reference_score_backward(g, ns, gs, x, Wq, bq, Wk, bk):
@@ -228,6 +339,7 @@ class SpGraphTransAttentionLayer(nn.Module):
             "Number of heads ({}) must be a factor of the dimension size ({})".format(self.h, self.attention_dim)
         self.d_k = self.attention_dim // self.h
         _check_supported(opt)
+        self.mix = bool(opt.get('mix_features', False))
         if opt.get('attention_type', 'scaled_dot') == "exp_kernel":
             self.output_var = nn.Parameter(torch.ones(1))
             self.lengthscale = nn.Parameter(torch.ones(1))
@@ -245,6 +357,8 @@ class SpGraphTransAttentionLayer(nn.Module):
         self._uniform = None  # (graph, NodeScores, m, rl, csr weights) for the uniform fast path
         self._wcat = None     # (param versions, ([Wq;Wk], [bq;bk]))
         self._sp_bufs = None  # (state shape, ops.SquareplusState): the squareplus operands
+        self._mixp = None     # (param versions, (Wv, bv, Wout, b_out)): mix_features
+        self._uniform_heads = None  # (graph, per-head weights [nnz, h]) of the uniform case: mix_features
 
     def init_weights(self, m):
         """Constant 1e-5 init (:153-157)."""
@@ -318,6 +432,33 @@ class SpGraphTransAttentionLayer(nn.Module):
         self.scores_and_stats(g, None, 0)
         return self._uniform[4]
 
+    def uniform_head_weights(self, g):
+        """The uniform case's per-head weights [nnz, h] (aggregation-CSR order; 1/outdeg in
+        every head), computed once per graph and cached beside ``_uniform`` (mix_features)."""
+        if self._uniform_heads is None or self._uniform_heads[0] is not g:
+            ns, m, rl = self.scores_and_stats(g, None, 0)
+            self._uniform_heads = (g, ops.head_weights(g, ns, m, rl, 0))
+        return self._uniform_heads[1]
+
+    def mix_params(self):
+        """(Wv [att, C], bv [att], Wout [C, dk], b_out [C]) contiguous, cached per parameter
+        version: the operands of the two products of mix_features (stable buffers, so
+        captured step graphs keep replaying)."""
+        ps = (self.V.weight, self.V.bias, self.Wout.weight, self.Wout.bias)
+        key = tuple(_tensor_key(t) for t in ps)
+        if self._mixp is None or self._mixp[0] != key:
+            self._mixp = (key, tuple(t.detach().contiguous() for t in ps))
+        return self._mixp[1]
+
+    def project(self, x):
+        """v = V(x) (:226) [.., attention_dim] fp32, head h in columns h*dk .. (mix_features)."""
+        if x.dtype != torch.float32:
+            raise NotImplementedError("gnpde: transformer mix_features runs on fp32 states only (got %s)" % x.dtype)
+        if _needs_grad(x, self.V.weight, self.V.bias):
+            return _MixProject.apply(x, self.V.weight, self.V.bias)
+        Wv, bv, _, _ = self.mix_params()
+        return ops.linear(x, Wv, bv)[0].view(tuple(x.shape[:-1]) + (self.attention_dim,))
+
     def uses_wcat(self):
         """Per-edge score modes project Q|K with one fused MFMA GEMM over [Wq; Wk]."""
         return self.score_mode != 'reference' or self.opt.get('attention_type', 'scaled_dot') != 'scaled_dot'
@@ -340,17 +481,26 @@ class SpGraphTransAttentionLayer(nn.Module):
     def forward(self, x, edge, y=None):
         """Returns (attention [B,E,h], (None, None)): the per-edge softmax
         attention of :265-266 in COO order.  ``values`` (V(x), prods) is not
-        materialised (dead for mix_features=False)."""
+        materialised (dead for mix_features=False).  Under mix_features:
+        (attention, (v, None)), v = V(x) in the reference's layout [B,N,dk,h] (:226-234:
+        a transposed view of the [B,N,h,dk] projection); ``prods`` stays unmaterialised."""
+        att = self.attention(x, edge)
+        if not self.mix:
+            return att, (None, None)
+        v = self.project(x)
+        return att, (v.view(tuple(v.shape[:-1]) + (self.h, self.d_k)).transpose(-1, -2), None)
+
+    def attention(self, x, edge):
+        """attention [B,E,h] (COO): forward's first output."""
         g = self.graph_for(x, edge)
         norm_idx = int(self.opt['attention_norm_idx'])
         ov = getattr(self, 'output_var', None)
         ls = getattr(self, 'lengthscale', None)
         if _needs_grad(x, self.Q.weight, self.Q.bias, self.K.weight, self.K.bias, ov, ls):
-            att = _EdgeAttention.apply(x, self.Q.weight, self.Q.bias, self.K.weight, self.K.bias, ov, ls, self, g,
-                                       norm_idx)
-            return att, (None, None)
+            return _EdgeAttention.apply(x, self.Q.weight, self.Q.bias, self.K.weight, self.K.bias, ov, ls, self, g,
+                                        norm_idx)
         ns, m, rl = self.scores_and_stats(g, x, norm_idx)
-        return self.edge_attention(g, ns, m, rl, norm_idx), (None, None)
+        return self.edge_attention(g, ns, m, rl, norm_idx)
 
     def __repr__(self):
         return self.__class__.__name__ + ' (' + str(self.in_features) + ' -> ' + str(self.out_features) + ')'
@@ -370,8 +520,22 @@ class ODEFuncTransformerAtt(ODEFunc):
         self.y = None
 
     def multiply_attention(self, x, attention, v=None):
-        """A_mean x with attention [B,E,h] given explicitly (:20-42)."""
+        """A_mean x with attention [B,E,h] given explicitly (:33-42); under mix_features
+        Wout(z) (:23-32), z the per-head aggregation of ``v`` (the layer's [B,N,dk,h]
+        values; V(x) when not given) with that attention."""
         g = self.graph_for(x)
+        lay = self.multihead_att_layer
+        if lay.mix:
+            if x.dtype != torch.float32:
+                raise NotImplementedError("gnpde: transformer mix_features runs on fp32 states only (got %s)"
+                                          % x.dtype)
+            if v is None:
+                vr = lay.project(x.detach())
+            else:  # [B,N,dk,h] -> [B,N,att] with head h in columns h*dk ..
+                vr = v.detach().float().transpose(-1, -2).reshape(g.B, g.N, lay.attention_dim)
+            z = ops.head_aggregate(g, attention.detach().float(), vr, coo=True)
+            _, _, Wo, bo = lay.mix_params()
+            return ops.linear_rhs(z, Wo, x.detach(), rhs=False, bias=bo)
         w = g.gather_weights(attention.detach().float())
         return ops.spmm_rhs(g, w, x, rhs=False)
 
@@ -388,6 +552,11 @@ class ODEFuncTransformerAtt(ODEFunc):
         g = self.graph_for(x)
         lay = self.multihead_att_layer
         st = [g]
+        if lay.mix:
+            # the cached contiguous V / Wout operands, and the uniform case's per-head weights
+            st.append(lay.mix_params())
+            if lay.is_uniform(int(self.opt['attention_norm_idx'])):
+                st.append(lay.uniform_head_weights(g))
         if lay.is_uniform(int(self.opt['attention_norm_idx'])):
             lay.uniform_weights(g)
             st.append(lay._uniform)
@@ -412,8 +581,10 @@ class ODEFuncTransformerAtt(ODEFunc):
         order); the key sum of the fork's scores (fp64, row-tile order) and the
         destination statistics (packed CSC edge blocks) are summed in another order,
         within fp64 / fp32 rounding (tests/test_gpu_layout.py).  Other attention
-        types keep the user numbering."""
+        types keep the user numbering, and so does mix_features."""
         lay = self.multihead_att_layer
+        if lay.mix:
+            return False
         return lay.is_uniform(int(self.opt['attention_norm_idx'])) or \
             self.opt.get('attention_type', 'scaled_dot') == 'scaled_dot'
 
@@ -421,7 +592,9 @@ class ODEFuncTransformerAtt(ODEFunc):
         """With the fork's scaled_dot under source-grouped softmax the weights do
         not depend on x (1/outdeg), so columns are independent and the fused
         integrator may pad the state (integrator._padded_width); score modes
-        read Q/K over all C columns and may not."""
+        read Q/K over all C columns and may not, nor does mix_features (V reads them)."""
+        if self.multihead_att_layer.mix:
+            return False
         return self.multihead_att_layer.is_uniform(int(self.opt['attention_norm_idx'])) and \
             not self.opt.get('add_source', False)
 
@@ -434,9 +607,12 @@ class ODEFuncTransformerAtt(ODEFunc):
         self.nfe += 1
         g = self.graph_for(x)
         lay = self.multihead_att_layer
+        if lay.mix and x.dtype != torch.float32:
+            raise NotImplementedError("gnpde: transformer mix_features runs on fp32 states only (got %s)" % x.dtype)
+        mixp = (lay.V.weight, lay.V.bias, lay.Wout.weight, lay.Wout.bias) if lay.mix else ()
         if stage is None and _needs_grad(x, self.alpha_train, self.beta_train, lay.Q.weight, lay.Q.bias,
                                          lay.K.weight, lay.K.bias, getattr(lay, 'output_var', None),
-                                         getattr(lay, 'lengthscale', None)):
+                                         getattr(lay, 'lengthscale', None), *mixp):
             return self._rhs_autograd(g, x)
         norm_idx = int(self.opt['attention_norm_idx'])
         add_source = bool(self.opt.get('add_source', False))
@@ -449,6 +625,18 @@ class ODEFuncTransformerAtt(ODEFunc):
         kw = dict(x0=x0, alpha=self.alpha_train.detach(), beta=self.beta_train.detach(),
                   rhs=True, alpha_sigmoid=not self.opt.get('no_alpha_sigmoid', False), add_source=add_source,
                   stage=stage)
+        if lay.mix:
+            # the value projection: per-head attention (cached for the uniform case), v = V(x),
+            # z by the per-head aggregation, then Wout with its bias and the RHS epilogue fused
+            if lay.is_uniform(norm_idx):
+                wh = lay.uniform_head_weights(g)
+            else:
+                wh = ops.head_weights(g, *lay.scores_and_stats(g, x, norm_idx), norm_idx)
+            Wv, bv, Wo, bo = lay.mix_params()
+            v = ops.linear(x, Wv, bv)[0]
+            z = ops.head_aggregate(g, wh, v)
+            # a solver stage takes f + the stage pass (the same bits as the kernel's fused stage)
+            return ops.linear_rhs(z, Wo, x, bias=bo, fuse=False, **kw)
         if lay.is_uniform(norm_idx):
             return ops.spmm_rhs(g, lay.uniform_weights(g), x, **kw)
         if lay.square_plus:
@@ -478,15 +666,20 @@ class ODEFuncTransformerAtt(ODEFunc):
     def _rhs_autograd(self, g, x):
         """Training forward: attention [B,E,h] through _EdgeAttention, then the
         Laplacian RHS autograd with those weights (head mean), so gradients
-        reach x (both paths), alpha, beta and the Q/K parameters."""
+        reach x (both paths), alpha, beta and the Q/K parameters.  Under mix_features
+        _MixRHS instead: x also through V, and V / Wout with their biases."""
         from .function_laplacian_diffusion import _LaplacianRHS
-        att, _ = self.multihead_att_layer(x, self.edge_index)
+        lay = self.multihead_att_layer
+        att = lay.attention(x, self.edge_index)
         add_source = bool(self.opt.get('add_source', False))
         if add_source and self.x0 is None:
             raise RuntimeError("ODEFuncTransformerAtt: add_source needs x0 (ODEblock.set_x0)")
         x0 = self.x0 if add_source else None
         if x0 is not None and x0.dtype != torch.float32:
             x0 = x0.float()
+        if lay.mix:
+            return _MixRHS.apply(x, self.alpha_train, self.beta_train, att, lay.V.weight, lay.V.bias, lay.Wout.weight,
+                                 lay.Wout.bias, g, x0, not self.opt.get('no_alpha_sigmoid', False), add_source)
         ad = att.detach()
         return _LaplacianRHS.apply(x, self.alpha_train, self.beta_train, att, g, g.gather_weights(ad),
                                    lambda: g.gather_weights(ad, transpose=True), x0,

@@ -1081,17 +1081,19 @@ def _linear_rhs_fuses(stage):
 
 
 def linear_rhs(z, Wt, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoid=True, add_source=False, out=None,
-               stage=None, fuse=True):
+               stage=None, fuse=True, bias=None):
     """f = a*(z Wt^T - x) [+ b*x0] (or z Wt^T with rhs=False): the output product of the
     GAT value projection with the RHS epilogue and the fixed-grid stage combination fused
     (gnpde_linear_rhs_f32).  z [..., K] fp32, Wt [C, K] fp32 (= Wout^T), x / x0 [..., C]
     fp32 with the rows of z.  stage: a ``Stage`` -> its outputs are written instead of f
     (returns None); a stage the kernel does not fuse (Stage.wide, a coefficient scale,
     out_rows, f_lin), or any stage with fuse=False, takes f first and the stage in a second
-    pass (stage_apply), as spmm_rhs does for on-the-fly weights — the same bits."""
+    pass (stage_apply), as spmm_rhs does for on-the-fly weights — the same bits.
+    bias [C] fp32: ax = z Wt^T + bias ahead of the epilogue (gnpde_linear_rhs_bias_f32, the
+    transformer layer's Wout); None: gnpde_linear_rhs_f32."""
     if stage is not None and not (fuse and _linear_rhs_fuses(stage)):
         f = linear_rhs(z, Wt, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
-                       add_source=add_source)
+                       add_source=add_source, bias=bias)
         stage_apply(stage, f, x, x)
         return None
     zr = _rows(z, "z")
@@ -1127,11 +1129,83 @@ def linear_rhs(z, Wt, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoid
         _require_gpu(out, "out", torch.float32)
         if not out.is_contiguous() or out.numel() != R * C:
             raise ValueError("linear_rhs: out must be contiguous and hold %d x %d" % (R, C))
-    _lib.call("gnpde_linear_rhs_f32", _ptr(zr), R, K, K, _ptr(Wt), C, _ptr(xr), C, _ptr(x0r), C, _ptr(a), _ptr(b),
-              _flags(rhs, alpha_sigmoid, add_source), _ptr(out), C, st, _stream(dev))
+    if bias is not None:
+        _require_gpu(bias, "bias", torch.float32)
+        bias = bias.contiguous()
+        if bias.numel() != C:
+            raise ValueError("linear_rhs: bias has %d elements, z Wt^T has %d columns" % (bias.numel(), C))
+        _lib.call("gnpde_linear_rhs_bias_f32", _ptr(zr), R, K, K, _ptr(Wt), C, _ptr(bias), _ptr(xr), C, _ptr(x0r), C,
+                  _ptr(a), _ptr(b), _flags(rhs, alpha_sigmoid, add_source), _ptr(out), C, st, _stream(dev))
+    else:
+        _lib.call("gnpde_linear_rhs_f32", _ptr(zr), R, K, K, _ptr(Wt), C, _ptr(xr), C, _ptr(x0r), C, _ptr(a), _ptr(b),
+                  _flags(rhs, alpha_sigmoid, add_source), _ptr(out), C, st, _stream(dev))
     if stage is not None:
         return None
     return out.view(x.shape if x is not None else tuple(z.shape[:-1]) + (C,))
+
+
+def head_aggregate(g, wh, v, coo=False, out=None):
+    """The per-head value aggregation of the transformer layer's mix_features branch
+    (gnpde_head_aggregate_f32, csrc/head_aggregate.hip):
+      z[r, d] = (1/H) sum_{p in row r} sum_h wh[p, h] * v[col[p], h*dk + d]      [B,N,dk]
+    v [B,N,att] (or [R,att]) fp32, head h owning columns h*dk .. h*dk+dk-1; wh the per-head
+    edge weights, [nnz, H] in aggregation-CSR order (head_weights), or with coo=True an
+    attention [B,E,H] in COO order (the layer's own output, an explicitly given one), which
+    the kernel reads through the CSR's perm.
+    Work items are K1's plan; no float atomics: repeated launches give the same bits."""
+    vr = _rows(v, "v")
+    _require_gpu(wh, "per-head weights", torch.float32)
+    wh = wh.contiguous()
+    H = int(wh.shape[-1])
+    att = vr.shape[1]
+    if wh.numel() != g.nnz * H or (coo and tuple(wh.shape) != (g.B, g.E, H)):
+        raise ValueError("head_aggregate: weights %s do not match %d edges x %d heads" % (tuple(wh.shape), g.nnz, H))
+    if H < 1 or att % H:
+        raise ValueError("head_aggregate: %d columns of v do not split into %d heads" % (att, H))
+    if vr.shape[0] != g.R:
+        raise ValueError("v has %d rows, graph has %d" % (vr.shape[0], g.R))
+    dk = att // H
+    dev = vr.device
+    if out is None:
+        out = torch.empty(g.R, dk, dtype=torch.float32, device=dev)
+    else:
+        _require_gpu(out, "out", torch.float32)
+        if not out.is_contiguous() or out.numel() != g.R * dk:
+            raise ValueError("head_aggregate: out must be contiguous and hold %d x %d" % (g.R, dk))
+    plan = g.csr.plan
+    nws = int(_lib.fn("gnpde_head_aggregate_workspace_floats")(dk, plan.n_slots))
+    if nws * 4 >= _PARTIALS_MAX_BYTES:
+        raise ValueError("gnpde: %d hub partial slots x %d columns exceed the 4 GiB of 32-bit buffer offsets the "
+                         "in-launch hub combine addresses; use a larger chunk (opt['gnpde_chunk'])"
+                         % (plan.n_slots, dk))
+    ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
+    plan.order_launch(dev)
+    _lib.call("gnpde_head_aggregate_f32", _ptr(plan.items), plan.n_items, _ptr(plan.heavy), plan.n_heavy,
+              _ptr(g.csr.rowptr), _ptr(g.csr.col), _ptr(g.csr.perm if coo else None), g.R, _ptr(wh), H, dk, _ptr(vr),
+              att, _ptr(out), dk, _ptr(ws), plan.n_slots, _stream(dev))
+    return out.view(tuple(v.shape[:-1]) + (dk,)) if v.dim() == 3 else out.view(g.R, dk)
+
+
+def head_weights(g, ns, m, rl, norm_idx):
+    """The per-head edge weights of head_aggregate for this RHS evaluation, [nnz, H] in
+    aggregation-CSR order: the layer's attention pass with a CSR-order output — ScoreArgs::score
+    with the group statistics (softmax: gnpde_edge_attention_csr_f32) or the squareplus operands
+    (m an ops.SquareplusState: gnpde_squareplus_attention_csr_f32), one pass for every
+    attention_type, score mode, grouping and normaliser; the values of edge_attention /
+    squareplus_attention, bit for bit, at att[perm[p]].  No head mean is formed.  (Measured
+    against head_aggregate reading the COO attention through perm: DESIGN.md §6.16.)"""
+    dev = g.csr.col.device
+    wh = torch.empty(max(g.nnz, 1), ns.heads, dtype=torch.float32, device=dev)
+    if isinstance(m, SquareplusState):
+        _sp_check_mode(ns)
+        _lib.call("gnpde_squareplus_attention_csr_f32", _ptr(g.csr.rowidx), _ptr(g.csr.col), _ptr(g.csr.perm), g.nnz,
+                  g.N, int(norm_idx), ns.mode, ns.heads, _ptr(m.pn), _ptr(m.sc), _ptr(m.M), _ptr(rl), _ptr(wh),
+                  _stream(dev))
+    else:
+        _lib.call("gnpde_edge_attention_csr_f32", _ptr(g.csr.rowidx), _ptr(g.csr.col), g.nnz, int(norm_idx), ns.mode,
+                  ns.heads, ns.dk, _ptr(ns.cs), _ptr(ns.q), _ptr(ns.k), ns.ldqk, ns.p0, ns.p1, _ptr(m), _ptr(rl),
+                  _ptr(wh), _stream(dev))
+    return wh[:g.nnz]
 
 
 class NodeScores(object):

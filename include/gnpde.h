@@ -470,6 +470,42 @@ int gnpde_linear_rhs_f32(const float* z, int64_t R, int64_t K, int64_t ldz,
                          float* f, int64_t ldf,
                          const gnpde_stage_epilogue_t* stage, void* stream);
 
+/* The same with an output bias (the transformer layer's Wout, an nn.Linear with a bias:
+ * function_transformer_attention.py:31; an entry point added under ABI 8):
+ *   ax[r,:] = sum_k z[r,k] * Wt[:,k] + bias[:]      bias [C] fp32, 16-byte aligned on the
+ * fast path; bias NULL: gnpde_linear_rhs_f32 itself (the same kernels, the same bits).
+ * The bias is added to the finished product ahead of the epilogue, on both kernels and
+ * under the fused stage.                                                          */
+int gnpde_linear_rhs_bias_f32(const float* z, int64_t R, int64_t K, int64_t ldz,
+                              const float* Wt /* [C, K] row-major */, int64_t C, const float* bias,
+                              const float* x, int64_t ldx, const float* x0, int64_t ldx0,
+                              const float* alpha, const float* beta, int flags,
+                              float* f, int64_t ldf,
+                              const gnpde_stage_epilogue_t* stage, void* stream);
+
+/* The per-head value aggregation of the transformer layer's mix_features branch
+ * (function_transformer_attention.py:23-32; entry points added under ABI 8):
+ *   z[r, d] = (1/heads) * sum over CSR positions p of row r, sum over h:
+ *                 w[p, h] * v[col[p], h*dk + d]          z [R, ldz] (dk columns)
+ * v [R, ldv] fp32 holds att = heads*dk columns, head h owning h*dk .. h*dk+dk-1.
+ * w: per-head edge weights, [nnz, heads] in aggregation-CSR order (perm NULL), or in COO
+ * order read as w[perm[p], h] (perm = the CSR's position -> COO edge map).  items / heavy:
+ * the plan of the aggregation CSR, consumed as gnpde_spmm_rhs_f32 consumes it (hub rows
+ * in chunk items, partial rows in `workspace`, combined in-launch by the last chunk to
+ * arrive, heavy[].w tickets reset for the next launch: launches on one plan must be
+ * ordered).  workspace: gnpde_head_aggregate_workspace_floats(dk, n_slots) floats,
+ * 16-byte aligned.  gnpde_head_aggregate_fast(heads, dk) != 0 (dk % 4 == 0, heads and
+ * heads*dk/4 powers of two, heads*dk <= 256) with 16-byte aligned rows: one wavefront per
+ * item; any other shape: one fp32 chain per output element over rowptr / col (the plan
+ * is not read).  No float atomics, fixed summation orders: repeated launches give the
+ * same bits.  A row without edges gets zeros.                                      */
+int gnpde_head_aggregate_fast(int64_t heads, int64_t dk);
+int64_t gnpde_head_aggregate_workspace_floats(int64_t dk, int64_t n_slots);
+int gnpde_head_aggregate_f32(const int32_t* items, int64_t n_items, int32_t* heavy, int64_t n_heavy,
+                             const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t R,
+                             const float* w, int64_t heads, int64_t dk, const float* v, int64_t ldv,
+                             float* z, int64_t ldz, float* workspace, int64_t n_slots, void* stream);
+
 /* Weight gradient of the projection: gW[m, k] = sum_r gy[r, m] * x[r, k]
  * (gy [R, M] ld ldg = dL/d[q | k], x [R, K] ld ldx; gW [M, K] ld ldw), the
  * backward of nn.Linear's weight for the Q / K of
@@ -599,6 +635,13 @@ int gnpde_edge_attention_f32(const int32_t* rowidx, const int32_t* col, const in
                              const double* cs, const float* q, const float* k, int64_t ldqk,
                              float score_p0, float score_p1, const double* m, const float* rl,
                              float* att, void* stream);
+/* The same values in aggregation-CSR order, att[p*heads + h] (no perm): the per-head
+ * weights of gnpde_head_aggregate_f32 (an entry point added under ABI 8).              */
+int gnpde_edge_attention_csr_f32(const int32_t* rowidx, const int32_t* col, int64_t nnz,
+                                 int norm_idx, int mode, int64_t heads, int64_t dk,
+                                 const double* cs, const float* q, const float* k, int64_t ldqk,
+                                 float score_p0, float score_p1, const double* m, const float* rl,
+                                 float* att, void* stream);
 
 /* ---------------------------------------------------------------- solver glue
  * out[i] = y0[i] + scale * sum_{j<nk} coef[j] * k_j[i]   (nk <= 8; y0 may be NULL = 0)
@@ -835,6 +878,12 @@ int gnpde_squareplus_weights_f32(const int32_t* rowidx, const int32_t* col, cons
 int gnpde_squareplus_attention_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
                                    int64_t N, int norm_idx, int mode, int64_t heads, const float* pn, const float* sc,
                                    const double* M, const float* rl, float* att, void* stream);
+/* gnpde_squareplus_attention_f32's values in aggregation-CSR order, att[p*heads + h] (perm still
+ * locates the stored scores sc of the per-edge modes): the per-head weights of
+ * gnpde_head_aggregate_f32 (an entry point added under ABI 8).                          */
+int gnpde_squareplus_attention_csr_f32(const int32_t* rowidx, const int32_t* col, const int32_t* perm, int64_t nnz,
+                                       int64_t N, int norm_idx, int mode, int64_t heads, const float* pn,
+                                       const float* sc, const double* M, const float* rl, float* att, void* stream);
 
 /* K1 with the squareplus weights of the reference scores under destination groups formed
  * in the gather loop: w_p = (1/heads) sum_h pn[row,h] * rl[col_p,h] (no transcendental per
