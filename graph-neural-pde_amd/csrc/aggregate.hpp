@@ -303,13 +303,10 @@ __device__ __forceinline__ void hub_sum(int first, int nch, int C, const float* 
 
 // Memory order of the arrival ticket.  The partials are stored write-through and
 // drained (s_waitcnt vmcnt(0)) before the ticket, which is what an agent-scope
-// release orders at the ISA level; GNPDE_HUB_RELEASE=1 builds the ticket as a
-// formal C++ release as well (it adds buffer_wbl2 sc1: a write-back of every
-// dirty line of the XCD's L2 before each chunk's ticket).
-#ifndef GNPDE_HUB_RELEASE
-#define GNPDE_HUB_RELEASE 0
-#endif
-constexpr int kHubTicketOrder = GNPDE_HUB_RELEASE ? __ATOMIC_RELEASE : __ATOMIC_RELAXED;
+// release orders at the ISA level.  The ticket is not a formal C++ release as
+// well: that adds buffer_wbl2 sc1, a write-back of every dirty line of the XCD's
+// L2 before each chunk's ticket.
+constexpr int kHubTicketOrder = __ATOMIC_RELAXED;
 
 // Chunk waves whose write-through partial stores are issued: drain them; each
 // row slot holding a hub chunk takes an arrival ticket on its hub's plan entry
@@ -371,8 +368,7 @@ __device__ __forceinline__ bool hub_claim(int4* heavy, int n_heavy, bool chunk, 
 // The hub combine of the flash kernels (flash.hip; agg_kernel uses hub_claim): each row slot of the wavefront that holds a
 // hub chunk takes its own ticket (its first lane); every slot whose chunk
 // arrived last is then combined by the WHOLE wavefront, one slot after the
-// other (hub_combine over 64 lanes: the same sums, in the same order, as
-// agg_fixup_kernel).  Called by all 64 lanes; `chunk` is per slot.
+// other (hub_combine over 64 lanes).  Called by all 64 lanes; `chunk` is per slot.
 template <int VEC, int GL, int SL, int RPW, int STG, class T>
 __device__ __forceinline__ void hub_arrive_slots(int4* heavy, int n_heavy, bool chunk, int slot, int C,
                                                  const Epi& ep, const float* partials) {
@@ -695,14 +691,7 @@ __global__ __launch_bounds__(256) void agg_kernel(const int4* __restrict__ items
       hub = hub_claim<VEC, GL, SL, RPW, NCH>(heavy, n_heavy, chunk, slot, C, partials, rs, g, gl, erow, acc);
       fin = fin || hub;
     }
-  } else if (live && slot >= 0 && g == 0) {  // chunk partials of a later agg_fixup_kernel
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int cc = (ch * GL + gl) * VEC;
-      if (cc < C) store_vec<VEC>(partials + (int64_t)slot * C + cc, acc[ch]);
-    }
-    return;
-  }
+  }  // (n_heavy == 0: no plan holds a chunk without its hub entry)
   if (!fin) return;
   if constexpr (PRE) {  // a hub row's epilogue operands were not prefetched
     if (hub) {
@@ -729,37 +718,16 @@ __global__ __launch_bounds__(256) void agg_kernel(const int4* __restrict__ items
   // the row's owner lanes (g == 0: lanes [rs*SL, rs*SL + GL)) are all here
   if constexpr (stage_rowsum<STG, T>()) {
     const double* prev = nullptr;
-    if constexpr (PRE && stage_dot<STG>() && GNPDE_DOT_PRE) prev = &pre[0].dprev;
+    if constexpr (PRE && stage_dot<STG>()) prev = &pre[0].dprev;
     epi_rowsums<GL, STG, T>(ep, erow, dpart, rs * SL, gl == 0, prev);
   }
 }
-
-// Hub rows combined after the aggregation launch (GNPDE_HUB_FIXUP=1): one wavefront per hub.
-template <int VEC, int GL, int STG, class T = float>
-__global__ __launch_bounds__(256) void agg_fixup_kernel(const int4* __restrict__ heavy, int n_heavy, int C, Epi ep,
-                                                         const float* __restrict__ partials) {
-  const int wid = uniform(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
-  if (wid >= n_heavy) return;
-  const int4 hv = heavy[wid];
-  hub_combine<VEC, pow2_ceil(GL), STG, T>(uniform(hv.x), uniform(hv.y), uniform(hv.z), C, ep, partials);
-}
-
-// Experiment builds only (make EXPERIMENTS=1 defines GNPDE_EXPERIMENTS=1; the
-// product library has none of this): GNPDE_HUB_FIXUP=1 combines hub rows in a
-// separate agg_fixup_kernel launch instead of inside the aggregation, and
-// GNPDE_AGG_VARIANT selects alternative lane geometries (the round-2 A/B sweeps
-// recorded in DESIGN.md §6-§7).
-bool hub_inlaunch();
-int agg_variant();
 
 template <int VEC, int GL, int NCH, int U, int RPW, class WP, class T = float>
 static int launch_agg_cfg(const int4* items, int64_t n_items, int4* heavy, int64_t n_heavy, const int* col,
                           const WP& wp, int C, const Epi& ep, float* partials, hipStream_t s) {
   const unsigned grid = (unsigned)ceil_div(n_items, (int64_t)kWavesPerBlock * RPW);
-  // hub rows are combined in the launch (hub_claim)
-  bool inlaunch = true;
-  if constexpr (GNPDE_EXPERIMENTS) inlaunch = hub_inlaunch();
-  const int nh = inlaunch ? (int)n_heavy : 0;
+  const int nh = (int)n_heavy;  // hub rows are combined in the launch (hub_claim)
   // single-output stages without dot terms (every forward gnpde.integrator step) get the
   // leaner instantiation: 56-60 VGPRs, 8 waves per SIMD; the dot terms of the adjoint
   // stages alone cost the general one 40+ VGPRs (fused rk4 K1 92.9 -> 107 us at 4 waves)
@@ -800,19 +768,6 @@ static int launch_agg_cfg(const int4* items, int64_t n_items, int4* heavy, int64
                                                                           partials);
     GNPDE_LAUNCH_CHECK();
   }
-  if constexpr (GNPDE_EXPERIMENTS) {
-    const unsigned gfix = (unsigned)ceil_div(n_heavy, kWavesPerBlock);
-    if (!inlaunch && n_heavy > 0) {
-      if (stg == 3 || stg == 4) stg = 2;
-      if (stg == 1)
-        agg_fixup_kernel<VEC, GL, 1, T><<<gfix, kBlock, 0, s>>>(heavy, (int)n_heavy, C, ep, partials);
-      else if (stg == 2)
-        agg_fixup_kernel<VEC, GL, 2, T><<<gfix, kBlock, 0, s>>>(heavy, (int)n_heavy, C, ep, partials);
-      else
-        agg_fixup_kernel<VEC, GL, 0, T><<<gfix, kBlock, 0, s>>>(heavy, (int)n_heavy, C, ep, partials);
-      GNPDE_LAUNCH_CHECK();
-    }
-  }
   return GNPDE_OK;
 }
 
@@ -824,34 +779,6 @@ static int launch_agg_vec(const int4* items, int64_t n_items, int4* heavy, int64
   const int lanes = (int)ceil_div(C, VEC);
 #define GNPDE_AGG(GL, NCH, U, RPW) \
   launch_agg_cfg<VEC, GL, NCH, U, RPW, WP, T>(items, n_items, heavy, n_heavy, col, wp, C, ep, partials, s)
-  const int var = GNPDE_EXPERIMENTS ? agg_variant() : 0;
-  if constexpr (GNPDE_EXPERIMENTS) {
-    switch (var) {
-      case 6:  // twice the gathers in flight per edge group
-        if (lanes <= 4) return GNPDE_AGG(4, 1, 8, 8);
-        if (lanes <= 8) return GNPDE_AGG(8, 1, 8, 4);
-        if (lanes <= 16) return GNPDE_AGG(16, 1, 8, 2);
-        break;
-      case 8:  // half the rows per wavefront, four edge groups per row
-        if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 4);
-        if (lanes <= 8) return GNPDE_AGG(8, 1, 4, 2);
-        if (lanes <= 16) return GNPDE_AGG(16, 1, 4, 1);
-        break;
-      // narrow stripes (the column layout at 4-8 ranks): edge groups per row x unroll
-      case 20: if (lanes <= 4) return GNPDE_AGG(4, 1, 8, 4); if (lanes <= 8) return GNPDE_AGG(8, 1, 4, 4); break;
-      case 21: if (lanes <= 4) return GNPDE_AGG(4, 1, 2, 4); if (lanes <= 8) return GNPDE_AGG(8, 1, 8, 2); break;
-      case 22: if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 8); if (lanes <= 8) return GNPDE_AGG(8, 1, 4, 2); break;
-      case 23: if (lanes <= 4) return GNPDE_AGG(4, 1, 8, 2); if (lanes <= 8) return GNPDE_AGG(8, 1, 2, 4); break;
-      case 24: if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 2); if (lanes <= 8) return GNPDE_AGG(8, 1, 8, 8); break;
-      case 2: if (lanes > 16 && lanes <= 32) return GNPDE_AGG(32, 1, 2, 1); break;
-      case 3:
-        if (lanes > 16 && lanes <= 32) return GNPDE_AGG(32, 1, 8, 1);
-        if (lanes > 32 && lanes <= 64) return GNPDE_AGG(64, 1, 8, 1);
-        break;
-      case 4: if (lanes > 16 && lanes <= 32) return GNPDE_AGG(32, 1, 4, 1); break;
-      default: break;
-    }
-  }
   // Narrow rows (the column stripes of gnpde.dist at 2-8 GPUs: G-arxiv C = 128 / 8 = 16
   // floats = 4 lanes; G-rmat 256 / 8 = 32 floats = 8 lanes): several rows per
   // wavefront with 2-4 edges side by side per row slot, instead of one row per
@@ -865,16 +792,14 @@ static int launch_agg_vec(const int4* items, int64_t n_items, int4* heavy, int64
   // (plain weights and the GAT policy, takes_narrow_rows: the reference-score policy takes
   // the 16-lane geometry for narrow rows, which keeps the library's instantiation count down)
   if constexpr (takes_narrow_rows<WP>::value) {
-    if (var != 5) {
-      if (n_items * (int64_t)C * (int64_t)sizeof(T) > (int64_t)(96 << 20)) {
-        if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 16);
-        if (lanes <= 8) return GNPDE_AGG(8, 1, 4, 8);
-        if (lanes <= 16) return GNPDE_AGG(16, 1, 4, 4);
-      }
-      if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 4);
-      if (lanes <= 8) return GNPDE_AGG(8, 1, 8, 4);
-      if (lanes <= 16) return GNPDE_AGG(16, 1, 4, 2);
+    if (n_items * (int64_t)C * (int64_t)sizeof(T) > (int64_t)(96 << 20)) {
+      if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 16);
+      if (lanes <= 8) return GNPDE_AGG(8, 1, 4, 8);
+      if (lanes <= 16) return GNPDE_AGG(16, 1, 4, 4);
     }
+    if (lanes <= 4) return GNPDE_AGG(4, 1, 4, 4);
+    if (lanes <= 8) return GNPDE_AGG(8, 1, 8, 4);
+    if (lanes <= 16) return GNPDE_AGG(16, 1, 4, 2);
   }
   if (lanes <= 16) return GNPDE_AGG(16, 1, 4, 1);
   if constexpr (sizeof(T) == 2 && VEC == 8) {
@@ -898,18 +823,13 @@ static int launch_agg_vec(const int4* items, int64_t n_items, int4* heavy, int64
 // Widest vector (elements per lane: 4, 2 or 1 floats; 8, 4, 2 or 1 bf16) every
 // operand of the aggregation and its epilogue allows: C, the leading dimensions
 // and all pointers must agree.
-// Experiment knob (not part of the ABI contract): GNPDE_BF16_VEC caps the
-// elements per lane of bf16 rows (default 4 = 8-byte gathers; 8 = 16-byte).
-int bf16_vec_cap();
-
 // bf16 rows are sized to land in 17-32 lanes, the two-rows-per-wavefront
 // geometry (launch_agg_vec): 8-byte gathers up to 128 columns, 16-byte gathers
 // for 129-256 columns (G-arxiv, items longest first: C = 128 58 us against 77-96;
 // BLEND C = 168 77 us against 93-122, 0.353-0.361 ms per rk4 step against 0.402).
 template <class T = float>
 inline int epi_vec_width(const Epi& ep, int64_t C, const void* partials) {
-  const int kMax = sizeof(T) == 2 ? ((C > 128 && C <= 256 && bf16_vec_cap() >= 4) ? 8 : bf16_vec_cap())
-                                  : 16 / (int)sizeof(T);
+  const int kMax = sizeof(T) == 2 ? ((C > 128 && C <= 256) ? 8 : 4) : 16 / (int)sizeof(T);
   for (int v = kMax; v > 1; v >>= 1) {
     const size_t bytes = (size_t)v * sizeof(T);
     auto al = [&](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; };

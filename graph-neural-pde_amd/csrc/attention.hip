@@ -147,15 +147,6 @@ __device__ __forceinline__ float seg_team_score(const ScoreArgs& sa, const float
 //     ticket.  Round 3 ran each hub group as one 1024-thread workgroup (mostly
 //     idle lanes, 16 wave slots held per group): the kernel took 20.9 us on
 //     G-arxiv's CSC, bound by those groups.
-// timing probes of experiment builds (GNPDE_RS_SKIP, launch_ref_stats): 1 / 2 skip the
-// hub + long / the short items, 4 stops a long item after its passes, 5 after its item load
-#if GNPDE_EXPERIMENTS
-__constant__ int g_rs_skip = 0;
-__device__ __forceinline__ int rs_skip() { return g_rs_skip; }
-#else
-__device__ __forceinline__ int rs_skip() { return 0; }
-#endif
-
 constexpr int kSegLongU = 8;                   // edges per lane
 constexpr int kSegLongMax = kWave * kSegLongU;  // 512: one pass
 
@@ -237,7 +228,6 @@ __device__ __forceinline__ void long_item_stats(int e0, int e1, const int* __res
     if (e0 + ps * LU * kWave >= e1) break;  // wave-uniform: an item of fewer edges skips the empty passes
     push_edges<LU, MAXH, GAT>(e0 + lane + ps * LU * kWave, kWave, e1, gidx, sa, M, L, grp, gid);
   }
-  if (GNPDE_EXPERIMENTS && rs_skip() == 4) return;
   wave_merge<MAXH>(M, L);
 }
 
@@ -377,12 +367,9 @@ __global__ __launch_bounds__(256) void seg_softmax_kernel(const int4* __restrict
 // A lane's segment end comes from a ballot of group changes (no rowptr gather).
 // Same arithmetic as seg_softmax_kernel<true, kSegStats>: segmented max,
 // exp(v - M), segmented sum, in the same lane order.
-#ifndef GNPDE_RS_NI
-#define GNPDE_RS_NI 1
-#endif
 // short items per wavefront: round 3 (1024-thread workgroups) 1 / 2 / 4 = 20.9 / 21.0 / 23.1 us;
-// round 4 (256-thread workgroups, hub chunks) 16.25 / 16.9 / 19.1 us (tools/ab_stats.sh)
-constexpr int kRefStatsNI = GNPDE_RS_NI;
+// round 4 (256-thread workgroups, hub chunks) 16.25 / 16.9 / 19.1 us
+constexpr int kRefStatsNI = 1;
 
 // GAT: the scores of mode GNPDE_SCORE_GAT (both endpoints' node scores) over the groups of
 // either grouping (gid: destination groups); the reference instantiations are unchanged.
@@ -394,17 +381,8 @@ __global__ __launch_bounds__(256) void ref_stats_kernel(const int4* __restrict__
                                                          float* __restrict__ rl, float* __restrict__ mr, int gid) {
   const int lane = threadIdx.x & 63;
   const int wid = uniform((int)blockIdx.x * kWavesPerBlock + (int)(threadIdx.x >> 6));
-  if constexpr (GNPDE_EXPERIMENTS) {  // timing probes: 1 skips the hub / long items, 2 the short ones
-    if (rs_skip() == 1 && wid < n_hub + n_long) return;
-    if (rs_skip() == 2 && wid >= n_hub + n_long) return;
-  }
   if (wid < n_hub + n_long) {
     const int4 it = items[wid];
-    if (GNPDE_EXPERIMENTS && rs_skip() == 5 && it.x == -7) return;  // (never: keeps the item load)
-    if (GNPDE_EXPERIMENTS && rs_skip() == 5) {
-      if (lane == 0 && it.y < 0) m[0] = 0.0;  // a use of the load, never taken
-      return;
-    }
     if (wid < n_hub) {
       hub_chunk_stats<MAXH, GAT>(uniform(it.x), uniform(it.y), uniform(it.z), uniform(it.w), gidx, sa, heavy, partials,
                                  m, rl, mr, gid);
@@ -463,14 +441,6 @@ template <int NI>
 static int launch_ref_stats(const int4* items, int64_t n_items, int64_t n_hub, int64_t n_long, const int* rowidx,
                             const int* gidx, const ScoreArgs& sa, int4* heavy, double* partials, double* m, float* rl,
                             float* mr, hipStream_t s, int gid = 1) {
-#if GNPDE_EXPERIMENTS
-  static const bool once = [] {  // GNPDE_RS_SKIP: the kernel's timing probes (before any capture)
-    const char* e = std::getenv("GNPDE_RS_SKIP");
-    const int v = e ? std::atoi(e) : 0;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_rs_skip), &v, sizeof(int)) == hipSuccess;
-  }();
-  (void)once;
-#endif
   const int64_t waves = n_hub + n_long + ceil_div(n_items - n_hub - n_long, (int64_t)NI);
   const unsigned grid = (unsigned)ceil_div(waves, (int64_t)kWavesPerBlock);
 #define GNPDE_RS(M)                                                                                            \

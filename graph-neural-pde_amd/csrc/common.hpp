@@ -8,13 +8,6 @@
 
 #include "../../include/gnpde.h"
 
-// Experiment builds (make EXPERIMENTS=1): the A/B knobs of the round-1/2 sweeps
-// (environment-selected K1 geometries, the separate hub fixup launch, the
-// XCD remap, the bf16 vector cap).  The product library is built without them.
-#ifndef GNPDE_EXPERIMENTS
-#define GNPDE_EXPERIMENTS 0
-#endif
-
 namespace gnpde {
 
 // ------------------------------------------------------------------ error plumbing
@@ -200,6 +193,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 // Workgroups are dispatched round-robin over the 8 XCDs (workgroup b runs on
 // XCD b % 8).  With remap on, XCD x is handed one contiguous run of the grid's
 // work instead of every 8th workgroup, so rows handled together share an L2.
+// (Measured slower at every setting, DESIGN.md §6.4: Epi::xcd_remap is always 0.)
 constexpr int kNumXcd = 8;
 __device__ __forceinline__ int xcd_block(int remap) {
   const int b = blockIdx.x;
@@ -221,7 +215,7 @@ __device__ __forceinline__ int xcd_block(int remap) {
 }
 
 struct Epi {
-  int xcd_remap;
+  int xcd_remap;  // always 0, nothing sets it: dropping the field costs one K1 instantiation a VGPR
   const float* x;
   int64_t ldx;
   const float* x0;
@@ -295,16 +289,6 @@ __device__ __forceinline__ float unpack(const Packed<VEC, bf16>& r, int t) {
 // so nothing in the load sequence branches.  Buffer byte offsets are 32-bit: a
 // wavefront any of whose rows lies past 4 GiB of the state takes the per-operand
 // form.
-// GNPDE_WIDE_BATCH=0 builds the per-operand form (A/B only).
-#ifndef GNPDE_WIDE_BATCH
-#define GNPDE_WIDE_BATCH 1
-#endif
-#ifndef GNPDE_WIDE_NOFB
-#define GNPDE_WIDE_NOFB 0
-#endif
-#ifndef GNPDE_STG4_PRE
-#define GNPDE_STG4_PRE 0  // wide-epilogue operand rows read before the gathers (A/B)
-#endif
 
 template <int VEC, class T>
 __device__ __forceinline__ void buf_load_packed(const void* p, uint32_t boff, Packed<VEC, T>& r) {
@@ -341,23 +325,16 @@ __device__ __forceinline__ void buf_load_packed(const void* p, uint32_t boff, Pa
 }
 
 // An operand row slice, or zeros for an absent operand (p == NULL, wave-uniform):
-// GNPDE_WIDE_SKIP=1 skips the absent operand's load under a scalar branch (an
-// out-of-range buffer load still costs an address-unit pass over the wavefront);
-// the waits stay at the first use after the whole batch.
-#ifndef GNPDE_WIDE_SKIP
-#define GNPDE_WIDE_SKIP 1
-#endif
+// the absent operand's load is skipped under a scalar branch (an out-of-range
+// buffer load still costs an address-unit pass over the wavefront); the waits
+// stay at the first use after the whole batch.
 template <int VEC, class T>
 __device__ __forceinline__ void opt_load(const float* p, uint32_t bo, Packed<VEC, T>& r) {
-  if (GNPDE_WIDE_SKIP) {
-    if (p) {
-      buf_load_packed<VEC, T>(p, bo, r);
-    } else {
-#pragma unroll
-      for (int t = 0; t < Packed<VEC, T>::W; ++t) r.d[t] = 0u;
-    }
+  if (p) {
+    buf_load_packed<VEC, T>(p, bo, r);
   } else {
-    buf_load_packed<VEC, T>(p, p ? bo : kBufNone, r);
+#pragma unroll
+    for (int t = 0; t < Packed<VEC, T>::W; ++t) r.d[t] = 0u;
   }
 }
 
@@ -445,38 +422,21 @@ template <int STG>
 constexpr bool stage_wide() {
   return STG == 4 || STG == 5;
 }
-// A/B knobs: whether the STG 1 / 2 / 3 instantiations prefetch their stage
-// operands before the gathers (1) or stream them after the aggregation (0, as STG 4)
-#ifndef GNPDE_STG1_PRE
-#define GNPDE_STG1_PRE 1
-#endif
-#ifndef GNPDE_STG2_PRE
-#define GNPDE_STG2_PRE 0  // 111 -> 69 VGPRs (4 -> 7 waves per SIMD)
-#endif
-#ifndef GNPDE_STG3_PRE
-#define GNPDE_STG3_PRE 0  // G-arxiv adjoint launch (CSC): 134 with, 117 us without (105 -> fewer VGPRs)
-#endif
-#ifndef GNPDE_DOT_PRE
-#define GNPDE_DOT_PRE 1   // the dot operand and the row's running dot read before the gathers: 128 -> 117 us
-#endif
-#ifndef GNPDE_DOT_DIAG
-#define GNPDE_DOT_DIAG 0  // diagnostics only (wrong results): 1 no dot arithmetic, 2 no row reduction / store
-#endif
-#ifndef GNPDE_ERR_DIAG
-#define GNPDE_ERR_DIAG 0  // diagnostics only (wrong results): bit 1 no error-term arithmetic, bit 2 no row sum
-// (G-arxiv K1 with error rows and no output, round 6: 116 us; bit 1: 106; bit 2: 91 — the per-row
-// error sum at the end of every wave costs ~20 us of a launch; whole-granule row stores: no change)
-#endif
-#ifndef GNPDE_STG2_DW
-#define GNPDE_STG2_DW 1   // STG 2 prefetches its dot operand too (with GNPDE_DOT_PRE)
-#endif
 template <int STG>
 constexpr int stage_nout() {
   return (STG == 2 || stage_wide<STG>()) ? 2 : 1;
 }
+// Only STG 1 prefetches its stage operands before the gathers; STG 2 and 3 stream
+// them after the aggregation, as STG 4 does.  Prefetching measured worse there:
+// STG 2 held 111 against 69 VGPRs (4 against 7 waves per SIMD), and STG 3 ran the
+// G-arxiv adjoint launch (CSC) in 134 against 117 us.  STG 2 and 3 do read the dot
+// operand and the row's running dot before the gathers (128 -> 117 us).
+// (G-arxiv K1 with error rows and no output, round 6: 116 us; without the error-term
+// arithmetic 106; without the row sum 91 — the per-row error sum at the end of every
+// wave costs ~20 us of a launch; whole-granule row stores: no change.)
 template <int STG>
 constexpr bool stage_prefetch() {
-  return (STG == 1 && GNPDE_STG1_PRE) || (STG == 2 && GNPDE_STG2_PRE) || (STG == 3 && GNPDE_STG3_PRE);
+  return STG == 1;
 }
 template <int STG>
 constexpr int stage_kpre() {  // operands prefetched before the gathers
@@ -491,10 +451,6 @@ constexpr bool stage_dot() {
   return STG == 2 || STG == 3;
 }
 template <int STG>
-constexpr bool stage_dw_pre() {  // the dot operand read before the gathers
-  return (STG == 2 && (stage_prefetch<STG>() || (GNPDE_DOT_PRE && GNPDE_STG2_DW))) || (STG == 3 && GNPDE_DOT_PRE);
-}
-template <int STG>
 constexpr bool stage_err() {
   return stage_wide<STG>();
 }
@@ -505,9 +461,8 @@ struct EpiPre {
   Packed<VEC, T> x0r;
   Packed<VEC, T> base[stage_bpre<STG>() > 0 ? stage_bpre<STG>() : 1];
   Packed<VEC, T> kv[stage_kpre<STG>() > 0 ? stage_kpre<STG>() : 1];
-  Packed<VEC, T> dw;  // the stage's dot operand (dot_rows; STG 2 with GNPDE_STG2_PRE, STG 3 with GNPDE_DOT_PRE)
+  Packed<VEC, T> dw;  // the stage's dot operand (dot_rows; STG 2, 3)
   double dprev;       // the row's running dot (dot_accumulate), read before the gathers
-  Packed<VEC, T> wk[(stage_wide<STG>() && GNPDE_STG4_PRE > 0) ? GNPDE_STG4_PRE : 1];  // the wide epilogue's first operands
 };
 
 // The Epi / stage pointers are declared float*; for bf16 storage they address
@@ -526,27 +481,8 @@ __device__ __forceinline__ void epi_prefetch(const Epi& e, int64_t row, int cc, 
   const bool need_x = (e.flags & GNPDE_EPI_RHS) != 0;
   if (need_x) load_packed<VEC>(as_t<T>(e.x) + row * e.ldx + cc, p.xr);
   if (e.flags & GNPDE_ADD_SOURCE) load_packed<VEC>(as_t<T>(e.x0) + row * e.ldx0 + cc, p.x0r);
-  if constexpr (stage_dot<STG>() && GNPDE_DOT_PRE)  // the running dot: its read is off the epilogue's chain
+  if constexpr (stage_dot<STG>())  // the running dot: its read is off the epilogue's chain
     p.dprev = (e.st.dot_rows && e.st.dot_accumulate) ? e.st.dot_rows[row] : 0.0;
-  if constexpr (stage_wide<STG>() && GNPDE_STG4_PRE > 0) {
-    // the first GNPDE_STG4_PRE present operand rows of the wide epilogue (WideSlots order)
-    const int64_t off = row * e.ldf + cc;
-    if (GNPDE_WIDE_BATCH && rows_fit_buffer<VEC, T>(off)) {
-      WideSlots<2, GNPDE_STAGE_MAX_K, true> w;
-      wide_slots<2, GNPDE_STAGE_MAX_K, true>(e.st, (need_x && e.ldx == e.ldf) ? e.x : nullptr, w);
-      const uint32_t bo = (uint32_t)(off * (int64_t)sizeof(T));
-      int cnt = 0;
-#pragma unroll
-      for (int q = 0; q < WideSlots<2, GNPDE_STAGE_MAX_K, true>::N; ++q) {
-        if (w.p[q]) {
-#pragma unroll
-          for (int c = 0; c < GNPDE_STG4_PRE; ++c)
-            if (cnt == c) buf_load_packed<VEC, T>(w.p[q], bo, p.wk[c]);
-          ++cnt;
-        }
-      }
-    }
-  }
   if constexpr (STG == 0 || stage_wide<STG>()) return;
   const int64_t off = row * e.ldf + cc;
 #pragma unroll
@@ -560,8 +496,8 @@ __device__ __forceinline__ void epi_prefetch(const Epi& e, int64_t row, int cc, 
 #pragma unroll
   for (int j = 0; j < stage_kpre<STG>(); ++j)
     if (j < e.st.nk && !(need_x && e.st.k[j] == e.x && e.ldx == e.ldf)) load_packed<VEC>(as_t<T>(e.st.k[j]) + off, p.kv[j]);
-  // the dot operand: STG 2 when prefetching, STG 2 / 3 under GNPDE_DOT_PRE (else in the epilogue)
-  if constexpr (stage_dw_pre<STG>())
+  // the dot operand (STG 2 / 3)
+  if constexpr (stage_dot<STG>())
     if (e.st.dot_rows) load_packed<VEC>(as_t<T>(e.st.dot_with) + off, p.dw);
 }
 
@@ -659,44 +595,26 @@ __device__ __forceinline__ void dense_coefs(const gnpde_stage_epilogue_t& st, fl
 // Returns the error combination in ev (when err_rows), output values in r and,
 // when y0v is given and err_rows is set, the tolerance's y0 row slice.  DENSE (STG
 // 5): also the dense output sum_q dc[q] * operand q in rd (base of output 0, k[j], f).
-template <int VEC, class T, int NKMAX = GNPDE_STAGE_MAX_K, int NOUT = 2, bool ERR = true, int PK = 0,
-          bool DENSE = false>
+template <int VEC, class T, int NKMAX = GNPDE_STAGE_MAX_K, int NOUT = 2, bool ERR = true, bool DENSE = false>
 __device__ __forceinline__ void wide_combine(const gnpde_stage_epilogue_t& st, int64_t off, const float (&o)[VEC],
                                              const float* xid, const float (&xv)[VEC], float (&r)[2][VEC],
                                              float (&ev)[VEC], Packed<VEC, T>* y0v = nullptr,
-                                             const Packed<VEC, T>* pre = nullptr, const float* dc = nullptr,
-                                             float* rd = nullptr) {
+                                             const float* dc = nullptr, float* rd = nullptr) {
   const float sc = stage_scale(st);
   float sco[NOUT];  // the outputs' coefficient scales (the error term's is sc)
 #pragma unroll
   for (int i = 0; i < NOUT; ++i) sco[i] = out_scale(st, i, sc);
-  if (GNPDE_WIDE_BATCH && (GNPDE_WIDE_NOFB || rows_fit_buffer<VEC, T>(off))) {
+  if (rows_fit_buffer<VEC, T>(off)) {
     const bool has_err = ERR && st.err_rows != nullptr;
     using WS = WideSlots<NOUT, NKMAX, ERR>;
     constexpr int N = WS::N;
     WS w;
     wide_slots<NOUT, NKMAX, ERR>(st, xid, w);
     const uint32_t bo = (uint32_t)(off * (int64_t)sizeof(T));
-    // every operand row issued before any is used (one memory round trip); the first PK
-    // present ones were read before the gathers (epi_prefetch, GNPDE_STG4_PRE)
+    // every operand row issued before any is used (one memory round trip)
     Packed<VEC, T> v[N];
-    int cnt = 0;
 #pragma unroll
-    for (int q = 0; q < N; ++q) {
-      bool from_pre = false;
-      if constexpr (PK > 0) {
-        if (pre && w.p[q]) {
-#pragma unroll
-          for (int c = 0; c < PK; ++c)
-            if (cnt == c) {
-              v[q] = pre[c];
-              from_pre = true;
-            }
-        }
-      }
-      if (!from_pre) opt_load<VEC, T>(w.p[q], bo, v[q]);
-      cnt += w.p[q] != nullptr;
-    }
+    for (int q = 0; q < N; ++q) opt_load<VEC, T>(w.p[q], bo, v[q]);
     const float* cb = w.cb;
 #pragma unroll
     for (int q = 0; q < N; ++q) {
@@ -858,11 +776,10 @@ __device__ __forceinline__ double err_terms(const gnpde_stage_epilogue_t& st, in
                                             const float (&y1)[VEC], const Packed<VEC, T>* y0pre = nullptr,
                                             double* aux = nullptr) {
   Packed<VEC, T> y0v;
-  if (GNPDE_WIDE_BATCH && y0pre)  // loaded with the operands (wide_combine)
+  if (y0pre)  // loaded with the operands (wide_combine)
     y0v = *y0pre;
   else
     load_packed<VEC>(as_t<T>(st.err_y0) + off, y0v);
-  if constexpr (GNPDE_ERR_DIAG & 1) return (double)ev[0] + (double)unpack(y0v, 0);
   const bool y0only = st.err_y1 == -2;
   const float at = (float)st.atol, rt = (float)st.rtol;
   float d = 0.f, a = 0.f;
@@ -923,9 +840,9 @@ __device__ __forceinline__ void epi_finish(const Epi& e, int64_t row, int cc, co
     for (int t = 0; t < VEC; ++t) xv[t] = need_x ? unpack(p.xr, t) : 0.f;
     DenseCoef dc;
     if constexpr (DENSE) dc = dense_load(e.st);
-    wide_combine<VEC, T, GNPDE_STAGE_MAX_K, 2, true, GNPDE_STG4_PRE, DENSE>(
-        e.st, off, o, (need_x && e.ldx == e.ldf) ? e.x : nullptr, xv, r, ev, &y0v, GNPDE_STG4_PRE > 0 ? p.wk : nullptr,
-        DENSE ? dc.c : nullptr, DENSE ? rd : nullptr);
+    wide_combine<VEC, T, GNPDE_STAGE_MAX_K, 2, true, DENSE>(e.st, off, o, (need_x && e.ldx == e.ldf) ? e.x : nullptr,
+                                                            xv, r, ev, &y0v, DENSE ? dc.c : nullptr,
+                                                            DENSE ? rd : nullptr);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       if (i < e.st.n_out) store_vec<VEC>(as_t<T>(e.st.o[i].out) + oo, r[i]);
@@ -956,17 +873,9 @@ __device__ __forceinline__ void epi_finish(const Epi& e, int64_t row, int cc, co
   } else {
     if constexpr (stage_dot<STG>()) {
       if (e.st.dot_rows && dpart) {
-        Packed<VEC, T> dw;
-        if constexpr (stage_dw_pre<STG>())
-          dw = p.dw;
-        else
-          load_packed<VEC>(as_t<T>(e.st.dot_with) + off, dw);
-        if constexpr (GNPDE_DOT_DIAG == 1) {
-          *dpart += (double)unpack(dw, 0);
-        } else {
+        // (the dot operand was read before the gathers: epi_prefetch)
 #pragma unroll
-          for (int t = 0; t < VEC; ++t) *dpart = fma((double)o[t], (double)unpack(dw, t), *dpart);
-        }
+        for (int t = 0; t < VEC; ++t) *dpart = fma((double)o[t], (double)unpack(p.dw, t), *dpart);
       }
     }
     const float sc = stage_scale(e.st);
@@ -1060,7 +969,7 @@ __device__ __forceinline__ float group_sum32(float v) {
   return v;
 }
 
-// prev: the row's running dot read before the gathers (GNPDE_DOT_PRE), or nullptr;
+// prev: the row's running dot read before the gathers, or nullptr;
 // dot_ch: the dot channel whatever err_rows says (the wide epilogue's second row sum)
 __device__ __forceinline__ void epi_rowsum_write(const Epi& e, int64_t row, double v, const double* prev = nullptr,
                                                  bool dot_ch = false) {
@@ -1083,7 +992,6 @@ template <int GL, bool F32 = false>
 __device__ __forceinline__ void epi_rowsum_store(const Epi& e, int64_t row, double dpart, bool store,
                                                  const double* prev = nullptr, bool dot_ch = false) {
   static_assert((GL & (GL - 1)) == 0, "the xor tree needs power-of-two row lanes");
-  if constexpr (GNPDE_DOT_DIAG == 2) return;
   if constexpr (F32)
     dpart = (double)group_sum32<GL>((float)dpart);
   else
@@ -1114,7 +1022,6 @@ __device__ __forceinline__ void epi_rowsums(const Epi& e, int64_t row, const dou
                                             const double* prev = nullptr) {
   if constexpr (stage_rowsum<STG, T>()) {
     if constexpr (stage_wide<STG>()) {
-      if constexpr (GNPDE_ERR_DIAG & 2) return;
       // the error / scale rows: fp32 slice sums (err_terms), reduced in fp32 and stored as fp64
       if (e.st.err_rows) epi_rowsum_store_any<GL, true>(e, row, dpart[0], base, store);
       if (e.st.scale_rows) {

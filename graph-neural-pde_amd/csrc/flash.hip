@@ -48,32 +48,11 @@ namespace gnpde {
 
 constexpr float kLog2e = 1.4426950408889634f;
 
-// A/B knobs of variant builds (make variant VFLAGS=...; the product build uses the defaults)
-#ifndef GNPDE_FL_PREFETCH
-#define GNPDE_FL_PREFETCH 0  // batch 0's first U gathers issued before pass 1 (195 against 176 us: registers)
-#endif
-#ifndef GNPDE_FL_TILEU
-#define GNPDE_FL_TILEU 4     // score-tile load instructions in flight
-#endif
-#ifndef GNPDE_FL_U
-#define GNPDE_FL_U 4         // edges in flight per row in the gather loop
-#endif
-#ifndef GNPDE_FL_DIAG
-#define GNPDE_FL_DIAG 0      // diagnostics only (wrong results): 1 no pass 1, 2 no pass-2 rescoring, 3 no slot reductions
-#endif
-#ifndef GNPDE_FL_DPPRED
-#define GNPDE_FL_DPPRED 1    // slot max / sum by DPP inside 16-lane rows (+ one swizzle per further row)
-#endif
-#ifndef GNPDE_FL_WAVES
-#define GNPDE_FL_WAVES 0     // amdgpu_waves_per_eu floor of the aggregation kernel (0: none)
-#endif
-
 struct DotArgs {
   const float* __restrict__ q;  // [R, ldqk]: q_r at q + r*ldqk, att = H*dk floats
   const float* __restrict__ k;
   int64_t ldqk;
   float scale;                  // log2(e) / sqrt(dk)
-  double scale64;               // the same in fp64 (the one-pass kernel's fp64 scores)
 };
 
 // sum over the S = dk/4 lanes of a head (S in {1, 2, 4, 8, 16}, aligned inside a 16-lane row)
@@ -90,16 +69,6 @@ __device__ __forceinline__ float head_reduce(float v) {
   return v;
 }
 
-// the same over fp64 values (dpp_mov64: common.hpp)
-template <int S>
-__device__ __forceinline__ double head_reduce64(double v) {
-  if constexpr (S >= 2) v += dpp_mov64<0xB1>(v);
-  if constexpr (S >= 4) v += dpp_mov64<0x4E>(v);
-  if constexpr (S >= 8) v += dpp_mov64<0x141>(v);
-  if constexpr (S >= 16) v += dpp_mov64<0x140>(v);
-  return v;
-}
-
 // Scores of n <= SL edges (destinations mc of lanes [base, base + n)) against
 // one row's q, in score tiles: NA = att/4 lanes per edge, each holding one
 // 16-byte slice of q (qv) and loading the same slice of its edge's k row, so one
@@ -107,7 +76,7 @@ __device__ __forceinline__ double head_reduce64(double v) {
 // re-reading a line another load already touched); the dk/4 lanes of a head
 // sum by DPP, and the head's first lane writes the score to the slot's LDS
 // scores sc[e][h].  kTileU instructions' loads are in flight together.
-constexpr int kTileU = GNPDE_FL_TILEU;
+constexpr int kTileU = 4;  // score-tile load instructions in flight
 
 template <int SL, int NA, int S, int H>
 __device__ __forceinline__ void tile_scores(const float (&qv)[4], int mc, int n, int base, int sl, const DotArgs& da,
@@ -143,35 +112,26 @@ __device__ __forceinline__ void own_scores(const float* __restrict__ sc, int sl,
   for (int h = 0; h < H; ++h) s[h] = sl < n ? sc[sl * H + h] : -INFINITY;
 }
 
-// xor trees over the SL lanes of a row slot (SL a power of two, slots aligned)
+// max / sum over the SL lanes of a row slot (SL a power of two >= 16, slots aligned):
+// by DPP inside 16-lane rows, plus one cross-lane shuffle per further row
 template <int SL>
 __device__ __forceinline__ float slot_max(float v) {
-  if constexpr (GNPDE_FL_DPPRED) {
-    v = fmaxf(v, dpp_mov<0xB1>(v));
-    v = fmaxf(v, dpp_mov<0x4E>(v));
-    v = fmaxf(v, dpp_mov<0x141>(v));
-    v = fmaxf(v, dpp_mov<0x140>(v));
+  v = fmaxf(v, dpp_mov<0xB1>(v));
+  v = fmaxf(v, dpp_mov<0x4E>(v));
+  v = fmaxf(v, dpp_mov<0x141>(v));
+  v = fmaxf(v, dpp_mov<0x140>(v));
 #pragma unroll
-    for (int o = 16; o < SL; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-  }
-#pragma unroll
-  for (int o = 1; o < SL; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
+  for (int o = 16; o < SL; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
 }
 template <int SL>
 __device__ __forceinline__ float slot_sum(float v) {
-  if constexpr (GNPDE_FL_DPPRED) {
-    v += dpp_mov<0xB1>(v);
-    v += dpp_mov<0x4E>(v);
-    v += dpp_mov<0x141>(v);
-    v += dpp_mov<0x140>(v);
+  v += dpp_mov<0xB1>(v);
+  v += dpp_mov<0x4E>(v);
+  v += dpp_mov<0x141>(v);
+  v += dpp_mov<0x140>(v);
 #pragma unroll
-    for (int o = 16; o < SL; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-  }
-#pragma unroll
-  for (int o = 1; o < SL; o <<= 1) v += __shfl_xor(v, o);
+  for (int o = 16; o < SL; o <<= 1) v += __shfl_xor(v, o);
   return v;
 }
 
@@ -247,12 +207,9 @@ __device__ __forceinline__ void dot_hub_combine(int row, int first, int nch, int
 
 // ------------------------------------------------------------------ the fused attention RHS
 template <int GL, int U, int NA, int S, int H, int STG>
-__global__ __launch_bounds__(256)
-#if GNPDE_FL_WAVES
-__attribute__((amdgpu_waves_per_eu(GNPDE_FL_WAVES)))
-#endif
-void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, int n_heavy,
-                    const int* __restrict__ col, DotArgs da, int C, Epi ep, float* __restrict__ partials) {
+__global__ __launch_bounds__(256) void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy,
+                                                       int n_heavy, const int* __restrict__ col, DotArgs da, int C,
+                                                       Epi ep, float* __restrict__ partials) {
   constexpr int RPW = kWave / GL;
   constexpr int SL = GL;
   __shared__ float scs[kWavesPerBlock][RPW][SL * H];  // each slot's batch scores
@@ -284,18 +241,8 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
 
   const int len = end - beg;
   const int mc0 = sl < len ? col[beg + sl] : 0;
-  // batch 0's first U gathers issued before pass 1 (A/B knob; off: the registers cost more)
-  float xv0[U][4];
-#pragma unroll
-  for (int u = 0; u < (GNPDE_FL_PREFETCH ? U : 0); ++u) {
-    const int c = __shfl(mc0, base + (u < len ? u : 0));
-    if (u < len && cc < C) {
-      load_vec<4>(ep.x + (int64_t)c * ep.ldx + cc, xv0[u]);
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) xv0[u][t] = 0.f;
-    }
-  }
+  // (issuing batch 0's first U gathers here, before pass 1, measured 195 against 176 us
+  // (registers): not done)
   float M[H], L[H], Rl[H];
   float s1[H];  // the lane's scores of batch 0 (kept for pass 2)
 #pragma unroll
@@ -304,7 +251,7 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
     L[h] = 0.f;
   }
   // pass 1: the statistics of the item's edges, batch by batch
-  for (int e0 = 0; e0 < (GNPDE_FL_DIAG == 1 ? 0 : len); e0 += SL) {
+  for (int e0 = 0; e0 < len; e0 += SL) {
     const int n = min(SL, len - e0);
     const int mc = e0 == 0 ? mc0 : (sl < n ? col[beg + e0 + sl] : 0);
     tile_scores<SL, NA, S, H>(qv, mc, n, base, sl, da, sc);
@@ -314,7 +261,6 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
 #pragma unroll
       for (int h = 0; h < H; ++h) s1[h] = s[h];
     }
-    if (GNPDE_FL_DIAG == 3) break;
 #pragma unroll
     for (int h = 0; h < H; ++h) {
       const float mb = slot_max<SL>(s[h]);  // inside the slot (slot-uniform control flow)
@@ -339,10 +285,10 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
       const int n = min(SL, len - e0);
       int mc;
       float s[H];
-      if (e0 == 0 || GNPDE_FL_DIAG) {
-        mc = e0 == 0 ? mc0 : (sl < n ? col[beg + e0 + sl] : 0);
+      if (e0 == 0) {
+        mc = mc0;
 #pragma unroll
-        for (int h = 0; h < H; ++h) s[h] = GNPDE_FL_DIAG == 1 ? 0.f : s1[h];
+        for (int h = 0; h < H; ++h) s[h] = s1[h];
       } else {  // a later batch of a long row: its scores again
         mc = sl < n ? col[beg + e0 + sl] : 0;
         tile_scores<SL, NA, S, H>(qv, mc, n, base, sl, da, sc);
@@ -358,10 +304,7 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
           const int src = base + (jj < n ? jj : 0);
           const int c = __shfl(mc, src);
           ww[u] = jj < n ? __shfl(mw, src) : 0.f;
-          if (GNPDE_FL_PREFETCH && e0 == 0 && j == 0) {  // gathered before pass 1
-#pragma unroll
-            for (int t = 0; t < 4; ++t) v[u][t] = xv0[u][t];
-          } else if (jj < n && cc < C) {
+          if (jj < n && cc < C) {
             load_vec<4>(ep.x + (int64_t)c * ep.ldx + cc, v[u]);
           } else {
 #pragma unroll
@@ -392,10 +335,10 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
     const int n = min(SL, len - e0);
     int mc;
     float s[H];
-    if (e0 == 0 || GNPDE_FL_DIAG) {
-      mc = e0 == 0 ? mc0 : (sl < n ? col[beg + e0 + sl] : 0);
+    if (e0 == 0) {
+      mc = mc0;
 #pragma unroll
-      for (int h = 0; h < H; ++h) s[h] = GNPDE_FL_DIAG == 1 ? 0.f : s1[h];
+      for (int h = 0; h < H; ++h) s[h] = s1[h];
     } else {
       mc = sl < n ? col[beg + e0 + sl] : 0;
       tile_scores<SL, NA, S, H>(qv, mc, n, base, sl, da, sc);
@@ -414,10 +357,7 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
         const int c = __shfl(mc, src);
 #pragma unroll
         for (int h = 0; h < H; ++h) ww[u][h] = jj < n ? __shfl(ph[h], src) : 0.f;
-        if (GNPDE_FL_PREFETCH && e0 == 0 && j < U) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) v[u][t] = xv0[(j + u) % U][t];
-        } else if (jj < n && cc < C) {
+        if (jj < n && cc < C) {
           load_vec<4>(ep.x + (int64_t)c * ep.ldx + cc, v[u]);
         } else {
 #pragma unroll
@@ -504,13 +444,8 @@ void dot_agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy, in
 // running rather than the final max (same value up to rounding).  Hub chunks
 // write their (acc_h, M_h rounded to fp32, L_h) and merge exactly as above
 // (dot_hub_combine).  G-arxiv per-edge RHS (norm_idx 0): 0.171 -> 0.151 ms.
-#ifndef GNPDE_FL_ONEPASS
-#define GNPDE_FL_ONEPASS 1   // A/B: 0 keeps the two-pass kernel above
-#endif
-#ifndef GNPDE_FL_SCORE64
-#define GNPDE_FL_SCORE64 0   // A/B: 1 head sums, scores and the running max in fp64 (0.202 against 0.151 ms)
-#endif
-using ScoreT = std::conditional_t<GNPDE_FL_SCORE64 != 0, double, float>;
+// (Head sums, scores and the running max in fp64 measured 0.202 against 0.151 ms: the
+// scores are fp32.)
 
 template <int GL, int U, int ATT, int H, int STG, class T = float>
 __global__ __launch_bounds__(256) void dot_agg1_kernel(const int4* __restrict__ items, int n_items, int4* heavy,
@@ -542,7 +477,7 @@ __global__ __launch_bounds__(256) void dot_agg1_kernel(const int4* __restrict__ 
   float qv[4];  // this lane's slice of the row's q (score tiles, as tile_scores)
   load_vec<4>(da.q + (int64_t)row * da.ldqk + 4 * sub, qv);
 
-  ScoreT M[H];
+  float M[H];
   float L[H], acch[H][4];
 #pragma unroll
   for (int h = 0; h < H; ++h) {
@@ -589,31 +524,28 @@ __global__ __launch_bounds__(256) void dot_agg1_kernel(const int4* __restrict__ 
         }
       }
       // the scores, summed exactly as tile_scores (four fmas, then the head's lanes by DPP)
-      ScoreT dt[TL];
+      float dt[TL];
 #pragma unroll
       for (int g = 0; g < TL; ++g) {
         float d = qv[0] * kt[g][0];
         d = fmaf(qv[1], kt[g][1], d);
         d = fmaf(qv[2], kt[g][2], d);
         d = fmaf(qv[3], kt[g][3], d);
-        if constexpr (GNPDE_FL_SCORE64)
-          dt[g] = head_reduce64<S>((double)d) * da.scale64;
-        else
-          dt[g] = head_reduce<S>(d) * da.scale;
+        dt[g] = head_reduce<S>(d) * da.scale;
       }
-      ScoreT sc[U][H];
+      float sc[U][H];
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int h = 0; h < H; ++h) {
-          const ScoreT x = __shfl(dt[u / EPI], base + (u % EPI) * NA + h * S);
+          const float x = __shfl(dt[u / EPI], base + (u % EPI) * NA + h * S);
           sc[u][h] = j + u < n ? x : -INFINITY;
         }
 #pragma unroll
       for (int h = 0; h < H; ++h) {
-        ScoreT mb = M[h];
+        float mb = M[h];
 #pragma unroll
-        for (int u = 0; u < U; ++u) mb = fmax(mb, sc[u][h]);
+        for (int u = 0; u < U; ++u) mb = fmaxf(mb, sc[u][h]);
         const float r = __builtin_amdgcn_exp2f((float)(M[h] - mb));  // M = -inf: 0 (the sums are 0 too)
         L[h] *= r;
 #pragma unroll
@@ -639,7 +571,8 @@ __global__ __launch_bounds__(256) void dot_agg1_kernel(const int4* __restrict__ 
       const int64_t pb = (int64_t)(chunk ? slot : 0) * ps;
 #pragma unroll
       for (int h = 0; h < H; ++h) {
-        // the slot keeps the max rounded to fp32, the sums taken relative to it
+        // the slot keeps the max rounded to fp32, the sums taken relative to it (fp32 scores:
+        // mf == M[h] and adj == 1; written out, the kernel's registers came out worse in places)
         const float mf = (float)M[h];
         const float adj = __builtin_amdgcn_exp2f((float)(M[h] - (double)mf));
         float av[4];
@@ -800,142 +733,21 @@ __global__ __launch_bounds__(256) void dot_dst_agg_kernel(const int4* __restrict
   (void)dpart;
 }
 
-// The one-pass form of the destination-grouped kernel (round 4, A/B knob
-// GNPDE_FL_DST1, off): each batch of U edges gathers the edges' x rows, their
-// k-row score tiles and their statistics records together, then weights and
-// accumulates (as dot_agg1_kernel; the score bits are those of tile_scores).
-// Measured: per-edge norm_idx 1 RHS 0.1706 against 0.1731 ms in the solve's
-// numbering, 0.1938 against 0.1851 in the user numbering (the per-batch record
-// loads) — not taken.
-#ifndef GNPDE_FL_DST1
-#define GNPDE_FL_DST1 0
-#endif
-template <int GL, int U, int ATT, int H, int STG>
-__global__ __launch_bounds__(256) void dot_dst_agg1_kernel(const int4* __restrict__ items, int n_items, int4* heavy,
-                                                            int n_heavy, const int* __restrict__ col, DotArgs da,
-                                                            const float* __restrict__ rec, int C, Epi ep,
-                                                            float* __restrict__ partials) {
-  constexpr int RPW = kWave / GL;
-  constexpr int SL = GL;
-  constexpr int RF = stats_record_floats(H);
-  constexpr int NA = ATT / 4;
-  constexpr int S = NA / H;
-  constexpr int EPI = SL / NA;
-  constexpr int TL = (U + EPI - 1) / EPI;
-  static_assert(NA <= SL && S >= 1 && S <= 16 && (S & (S - 1)) == 0, "dot_dst_agg1: score tile layout");
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int rs = lane / SL, sl = lane % SL;
-  const int wid = uniform(blockIdx.x * kWavesPerBlock + wv);
-  const int item = wid * RPW + rs;
-  if (wid * RPW >= n_items) return;
-  const bool live = item < n_items;
-  const int4 it = live ? items[item] : make_int4(0, 0, 0, -1);
-  const int row = it.x, beg = it.y, end = it.z, slot = it.w;
-  const int cc = sl * 4;
-  const bool owner = live && slot < 0 && cc < C;
-  const int base = rs * SL;
-  const int sub = sl % NA, eo = sl / NA;
-
-  EpiPre<4, float, STG> pre;
-  if (owner) epi_prefetch<4, STG, float>(ep, row, cc, pre);
-  float qv[4];
-  load_vec<4>(da.q + (int64_t)row * da.ldqk + 4 * sub, qv);
-  const int len = end - beg;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int e0 = 0; e0 < len; e0 += SL) {
-    const int n = min(SL, len - e0);
-    const int mc = sl < n ? col[beg + e0 + sl] : 0;
-    for (int j = 0; j < n; j += U) {
-      float v[U][4], kt[TL][4], rm[U][H], rr[U][H];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int jj = j + u;
-        const int c = __shfl(mc, base + (jj < n ? jj : 0));
-        if (jj < n && cc < C) {
-          load_vec<4>(ep.x + (int64_t)c * ep.ldx + cc, v[u]);
-        } else {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) v[u][t] = 0.f;
-        }
-        // the destination's statistics record (one line; the same address across the slot)
-        if constexpr (RF == 4 && H == 2) {
-          const float4 r4 = *reinterpret_cast<const float4*>(rec + (int64_t)c * 4);
-          rm[u][0] = r4.x; rm[u][1] = r4.y; rr[u][0] = r4.z; rr[u][1] = r4.w;
-        } else {
-#pragma unroll
-          for (int h = 0; h < H; ++h) {
-            rm[u][h] = rec[(int64_t)c * RF + h];
-            rr[u][h] = rec[(int64_t)c * RF + H + h];
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < TL; ++g) {
-        const int ue = g * EPI + eo;
-        const int jj = j + ue;
-        const int c = __shfl(mc, base + (jj < n ? jj : 0));
-        if (ue < U && jj < n) {
-          load_vec<4>(da.k + (int64_t)c * da.ldqk + 4 * sub, kt[g]);
-        } else {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) kt[g][t] = 0.f;
-        }
-      }
-      float dt[TL];
-#pragma unroll
-      for (int g = 0; g < TL; ++g) {
-        float d = qv[0] * kt[g][0];
-        d = fmaf(qv[1], kt[g][1], d);
-        d = fmaf(qv[2], kt[g][2], d);
-        d = fmaf(qv[3], kt[g][3], d);
-        dt[g] = head_reduce<S>(d) * da.scale;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        float w = 0.f;
-#pragma unroll
-        for (int h = 0; h < H; ++h) {
-          const float sh = __shfl(dt[u / EPI], base + (u % EPI) * NA + h * S);
-          w = fmaf(__builtin_amdgcn_exp2f(sh - rm[u][h] * kLog2e), rr[u][h], w);
-        }
-        constexpr float inv_h = 1.0f / (float)H;
-        w = j + u < n ? w * inv_h : 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = fmaf(w, v[u][t], acc[t]);
-      }
-    }
-  }
-  if (n_heavy > 0) {  // hub chunks: write-through partials, merged in-launch by the last arrival (K1's)
-    const bool chunk = live && slot >= 0;
-    int anyc = 0;
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) anyc |= __shfl((int)chunk, r * SL);
-    if (anyc) {  // wave-uniform
-      const __amdgpu_buffer_rsrc_t rp = buf_rsrc(partials);
-      buf_store_wt<4>(rp, (chunk && cc < C) ? (uint32_t)(((int64_t)slot * C + cc) * 4) : kBufNone, acc);
-      hub_arrive_slots<4, GL, SL, RPW, STG, float>(heavy, n_heavy, chunk, slot, C, ep, partials);
-      if (chunk) return;
-    }
-  }
-  if (!live || slot >= 0) return;
-  const float a = (ep.flags & GNPDE_EPI_RHS) ? epi_alpha(ep) : 1.f;
-  const float b = (ep.flags & GNPDE_ADD_SOURCE) ? *ep.beta : 0.f;
-  double dpart = 0.0;
-  if (owner) epi_finish<4, STG, float>(ep, row, cc, acc, a, b, pre, &dpart);
-  (void)dpart;
-}
-
+// (A one-pass form of this kernel, each batch of U edges gathering the edges' x rows, k-row
+// score tiles and statistics records together as dot_agg1_kernel does, measured 0.1706
+// against 0.1731 ms per norm_idx 1 RHS in the solve's numbering but 0.1938 against 0.1851 in
+// the user numbering (the per-batch record loads): not taken; it is in git history.)
 template <int GL, int NA, int S, int H, class T = float>
 static int launch_dot_nh(const int4* items, int64_t n_items, int4* heavy, int64_t n_heavy, const int* col,
                          const DotArgs& da, const float* rec, int C, const Epi& ep, float* partials, hipStream_t s) {
   constexpr int RPW = kWave / GL;
-  constexpr int U = GNPDE_FL_U;
+  constexpr int U = 4;  // edges in flight per row in the gather loop
   const unsigned grid = (unsigned)ceil_div(n_items, (int64_t)kWavesPerBlock * RPW);
   const int stg = epi_stage_kind(ep);
   const int nh = (int)n_heavy;
   if constexpr (sizeof(T) != 4) {
     // a bf16 state: the one-pass source-grouped kernel only (the caller takes K2 + the bf16 K1 otherwise)
-    if (rec != nullptr || stg >= 2 || !(GNPDE_FL_ONEPASS && NA <= GL)) {
+    if (rec != nullptr || stg >= 2 || NA > GL) {
       set_error("attn_dot_rhs_bf16: only the source-grouped plain RHS and single-output stages are fused");
       return GNPDE_EUNSUPPORTED;
     }
@@ -949,18 +761,6 @@ static int launch_dot_nh(const int4* items, int64_t n_items, int4* heavy, int64_
     return GNPDE_OK;
   }
   if (rec != nullptr) {  // destination-grouped softmax (norm_idx 1): statistics records given
-    if constexpr (GNPDE_FL_DST1 && 4 * NA <= 4 * GL) {
-      if (stg <= 1) {
-        if (stg == 1)
-          dot_dst_agg1_kernel<GL, U, 4 * NA, H, 1><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, da,
-                                                                            rec, C, ep, partials);
-        else
-          dot_dst_agg1_kernel<GL, U, 4 * NA, H, 0><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, da,
-                                                                            rec, C, ep, partials);
-        GNPDE_LAUNCH_CHECK();
-        return GNPDE_OK;
-      }
-    }
     if (stg == 1)
       dot_dst_agg_kernel<GL, U, NA, S, H, 1><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, da, rec, C,
                                                                       ep, partials);
@@ -974,7 +774,7 @@ static int launch_dot_nh(const int4* items, int64_t n_items, int4* heavy, int64_
     return GNPDE_OK;
   }
   constexpr int ATT = 4 * NA;
-  if constexpr (GNPDE_FL_ONEPASS && NA <= GL) {
+  if constexpr (NA <= GL) {
     if (stg == 1)
       dot_agg1_kernel<GL, U, ATT, H, 1><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, da, C, ep,
                                                                  partials);
@@ -1082,7 +882,6 @@ static int attn_dot_rhs_impl(const int32_t* items, int64_t n_items, int32_t* hea
   da.k = k;
   da.ldqk = ldqk;
   da.scale = kLog2e / sqrtf((float)dk);
-  da.scale64 = 1.4426950408889634 / sqrt((double)dk);
   const int4* it = reinterpret_cast<const int4*>(items);
   int4* hv = reinterpret_cast<int4*>(heavy);
   const int lanes = (int)(C / 4);

@@ -434,31 +434,12 @@ using namespace gnpde;
 // slot per row against bank conflicts, 3 waves per CU to fit 48 KB of W fragments +
 // 96 KB of tiles): 39.7 us against 33 us — one wave per SIMD at most cannot hide
 // the next tile's latency behind one tile of matrix work.
-// Experiment builds only (GNPDE_EXPERIMENTS): GNPDE_LINEAR=1 forces the
-// per-tile (non-persistent) exact-f32 kernel, =2 the persistent exact-f32 one
-// (default: the split-bf16 kernel where K % 16 == 0 and K <= 128).  Measured
-// and dropped: 16-row tiles on 16x16x32 with a three-deep register ring of x
-// tiles (31.7-32.3 us), splitting the whole tile before refilling (1 wave per
+// Kernel choice: the split-bf16 kernel where K % 16 == 0 and K <= 128, else the
+// persistent exact-f32 kernel (up to six LDS chunks), else the per-tile one.
+// Measured and dropped: 16-row tiles on 16x16x32 with a three-deep register ring
+// of x tiles (31.7-32.3 us), splitting the whole tile before refilling (1 wave per
 // SIMD, 32-38 us), refilling per step instead of per 128-byte line (32 us).
-static int linear_variant() {
-  if constexpr (!GNPDE_EXPERIMENTS) return 0;
-  static const int v = [] {
-    const char* e = std::getenv("GNPDE_LINEAR");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-
-// Experiment builds only: GNPDE_LIN_WAVES = wavefronts of the
-// persistent projection grid (default 2048).
-static int64_t linear_waves() {
-  if constexpr (!GNPDE_EXPERIMENTS) return 2048;
-  static const int64_t v = [] {
-    const char* e = std::getenv("GNPDE_LIN_WAVES");
-    return e ? std::max<int64_t>(4, std::atoll(e)) : (int64_t)2048;
-  }();
-  return v;
-}
+constexpr int64_t kLinWaves = 2048;  // wavefronts of the persistent projection grid
 
 template <class XT>
 static int linear_impl(const XT* x, int64_t R, int64_t K, int64_t ldx, const float* W, const float* bias, int64_t Nout,
@@ -479,12 +460,12 @@ static int linear_impl(const XT* x, int64_t R, int64_t K, int64_t ldx, const flo
   const bool vec4 = (K % 8 == 0) && (ldx % 4 == 0) && (sizeof(XT) == 4 ? aligned16(x) : aligned8(x));
   hipStream_t s = as_stream(stream);
   const int nch = (int)(Khp / kLinChunk);
-  if (vec4 && K % 16 == 0 && K <= 128 && aligned16(W) && linear_variant() == 0 &&
+  if (vec4 && K % 16 == 0 && K <= 128 && aligned16(W) &&
       R * std::max(lda, split == Nout ? lda : ldb) * (int64_t)sizeof(float) < (int64_t)kBufRecords) {
     // split-bf16 MFMA, persistent tiles (same wave budget as below)
     const int64_t ntiles = ceil_div(R, kLinRowsPerWave);
     const int64_t slices = ceil_div(Nout, kLinCols);
-    const int64_t max_waves = std::max<int64_t>(kWavesPerBlock, linear_waves() / slices);
+    const int64_t max_waves = std::max<int64_t>(kWavesPerBlock, kLinWaves / slices);
     const int64_t per_wave = ceil_div(ntiles, max_waves);
     const int64_t blocks = ceil_div(ceil_div(ntiles, per_wave), kWavesPerBlock);
     const dim3 gt((unsigned)blocks, (unsigned)slices);
@@ -514,11 +495,11 @@ static int linear_impl(const XT* x, int64_t R, int64_t K, int64_t ldx, const flo
     GNPDE_LAUNCH_CHECK();
     return GNPDE_OK;
   }
-  if (vec4 && nch <= 6 && linear_variant() != 1) {
+  if (vec4 && nch <= 6) {
     // persistent tiles: about 2 workgroups per CU, tiles spread evenly over the wavefronts
     const int64_t ntiles = ceil_div(R, kLinRowsPerWave);
     const int64_t slices = ceil_div(Nout, kLinCols);
-    const int64_t max_waves = std::max<int64_t>(kWavesPerBlock, linear_waves() / slices);
+    const int64_t max_waves = std::max<int64_t>(kWavesPerBlock, kLinWaves / slices);
     const int64_t per_wave = ceil_div(ntiles, max_waves);
     const int64_t blocks = ceil_div(ceil_div(ntiles, per_wave), kWavesPerBlock);
     const dim3 gt((unsigned)blocks, (unsigned)slices);

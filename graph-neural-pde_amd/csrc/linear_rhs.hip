@@ -208,7 +208,6 @@ static int linear_rhs_impl(const float* z, int64_t R, int64_t K, int64_t ldz, co
   GNPDE_REQUIRE(!rhs || x, GNPDE_EINVAL, "linear_rhs: NULL x");
   // (the plain product reads no x: the epilogue helpers never touch the stand-in)
   Epi e = make_epi(rhs ? x : z, rhs ? ldx : ldf, x0, ldx0, alpha, beta, flags, f, ldf, stage);
-  e.xcd_remap = 0;
   int rc = check_epi(e, C, 0, nullptr, 0);
   if (rc) return rc;
   if (stage) {

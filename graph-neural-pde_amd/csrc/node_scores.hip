@@ -260,10 +260,9 @@ __global__ __launch_bounds__(256) void attn_team_kernel(const int* __restrict__ 
 // KS_BLOCK threads per tile, TPR threads per row, RPB = KS_BLOCK/TPR rows in
 // flight per iteration (16-byte loads, 8 rows unrolled per thread).
 constexpr int kKeysumBlock = 1024;
-#ifndef GNPDE_KS_ROWS
-#define GNPDE_KS_ROWS 4  // 4 / 8 / 12: 0.1423 / 0.1429 / 0.1437 ms per reference RHS (with ring depth 2 / 4 / 6)
-#endif
-constexpr int kKeysumRows = GNPDE_KS_ROWS;  // rows per thread in flight (keysum_partial)
+// rows per thread in flight (keysum_partial): 4 / 8 / 12 measured 0.1423 / 0.1429 / 0.1437 ms
+// per reference RHS (with ring depth 2 / 4 / 6)
+constexpr int kKeysumRows = 4;
 constexpr int kKeysumTilesTarget = 256;  // tiles per launch: the projection block reads them all
 constexpr int kProjLanes = 32;           // lanes per row of Wk (S phase)
 constexpr int kProjLoads = 16;           // tile shares in flight per thread (key_projection)
@@ -512,14 +511,12 @@ __device__ __forceinline__ void ns_store(double (&acc)[MAXH], const double (&vb)
 // Prefetch addresses past the block's rows clamp to its last row (a cache-line
 // hit, no extra HBM traffic).  ns_first_rows issues the first kNsDepth groups,
 // before U exists when the block forms U itself (node_scores_fused_kernel).
-#ifndef GNPDE_NS_DEPTH
-#define GNPDE_NS_DEPTH 2  // deeper rings measured no faster (above)
-#endif
-// depth per head count: GNPDE_NS_DEPTH groups of NPV floats, capped at 64 floats of ring
+constexpr int kNsDepthMax = 2;  // deeper rings measured no faster (above)
+// depth per head count: kNsDepthMax groups of NPV floats, capped at 64 floats of ring
 template <int MAXH>
 constexpr int ns_depth() {
   constexpr int d = 64 / node_scores_npv<MAXH>();
-  return d < 2 ? 2 : (d > GNPDE_NS_DEPTH ? GNPDE_NS_DEPTH : d);
+  return d < 2 ? 2 : (d > kNsDepthMax ? kNsDepthMax : d);
 }
 
 template <int VEC, int GL, int MAXH>
@@ -629,11 +626,10 @@ __global__ __launch_bounds__(256) void node_scores_kernel(const float* __restric
 // per grid row (gridDim.y == B).
 constexpr int kNsfPre = 16;    // Wq values per U output held in registers (dk <= 16)
 constexpr int kNsfLoads = 32;  // tile shares in flight per thread
-#ifndef GNPDE_NSF_OUTS
-#define GNPDE_NSF_OUTS 1  // 4 (the 8-head Cora shape's U in one load round): 18.9 against 16.2 us
-#endif
-constexpr int kNsfOuts = GNPDE_NSF_OUTS;
-constexpr int64_t kNsSplitRows = 50000;  // below: key_projection_kernel + node_scores_kernel  // U outputs per thread with their Wq values in registers
+// U outputs per thread with their Wq values in registers: 4 (the 8-head Cora shape's U in
+// one load round) measured 18.9 against 16.2 us
+constexpr int kNsfOuts = 1;
+constexpr int64_t kNsSplitRows = 50000;  // below: key_projection_kernel + node_scores_kernel
 
 template <int VEC, int GL, int MAXH, bool CLAMP>
 __global__ __launch_bounds__(256) void node_scores_fused_kernel(const float* __restrict__ x, int64_t N, int C,
@@ -770,18 +766,8 @@ static int keysum_vec(int64_t C, const float* x, int64_t ldx) {
 
 // tiles of rows for the partial column sums (independent of the vector width):
 // about kKeysumTilesTarget over the launch, at least one row per row slot
-static int keysum_tiles_target() {
-  if constexpr (!GNPDE_EXPERIMENTS) return kKeysumTilesTarget;
-  static const int t = [] {
-    const char* e = std::getenv("GNPDE_KEYSUM_TILES");  // tuning knob (experiment builds)
-    const int v = e ? std::atoi(e) : 0;
-    return v >= 8 && v <= 4096 ? v : kKeysumTilesTarget;
-  }();
-  return t;
-}
-
 static void keysum_tiles(int64_t B, int64_t N, int rpb, int* rows_per_tile, int* ntiles) {
-  const int64_t per_batch = std::max<int64_t>(1, keysum_tiles_target() / B);
+  const int64_t per_batch = std::max<int64_t>(1, kKeysumTilesTarget / B);
   const int64_t rpt = std::max<int64_t>(ceil_div(N, per_batch), rpb);
   *rows_per_tile = (int)rpt;
   *ntiles = (int)ceil_div(N, rpt);
@@ -867,16 +853,6 @@ static void launch_node_scores_any(hipStream_t s, const NsGeom& ge, const float*
     }
   }
 #undef GNPDE_NS
-}
-
-// Experiment builds: GNPDE_NS_FUSED=0 keeps the separate key_projection launch.
-static bool ns_fused_enabled() {
-  if constexpr (!GNPDE_EXPERIMENTS) return true;
-  static const bool v = [] {
-    const char* e = std::getenv("GNPDE_NS_FUSED");
-    return !(e && e[0] == '0');
-  }();
-  return v;
 }
 
 template <int VEC, int GL, int MAXH>
@@ -1114,7 +1090,7 @@ static int ref_node_scores_launch(const float* x, int64_t B, int64_t N, int64_t 
   // small graphs (B N < kNsSplitRows: the launch is a handful of rows per workgroup) take
   // the projection once, in its own workgroup, instead of in every node-score workgroup:
   // Cora-sized 8-head scores 6.3 + 6.7 us against 16.2 us fused
-  if (ge.nch == 1 && att <= 1024 && B <= 65535 && B * N >= kNsSplitRows && ns_fused_enabled()) {
+  if (ge.nch == 1 && att <= 1024 && B <= 65535 && B * N >= kNsSplitRows) {
     // every node-score workgroup forms U itself (node_scores_fused_kernel): two launches
     launch_node_scores_fused(s, ge, x, B, N, (int)C, ldx, (int)heads, part, ntiles, Wq, bq, (int)att, cs);
     GNPDE_LAUNCH_CHECK();

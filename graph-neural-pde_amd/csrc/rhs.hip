@@ -4,40 +4,6 @@
 #include "aggregate.hpp"
 #include "rhs_host.hpp"
 
-namespace gnpde {
-
-int bf16_vec_cap() {
-  if constexpr (!GNPDE_EXPERIMENTS) return 4;
-  static const int v = [] {
-    // cap of the elements per lane (default 4 = 8-byte gathers); rows of 129-256 columns take
-    // 16-byte gathers anyway (epi_vec_width) so that they fit the two-rows-per-wavefront geometry
-    const char* e = std::getenv("GNPDE_BF16_VEC");
-    const int c = e ? std::atoi(e) : 4;
-    return (c == 1 || c == 2 || c == 8) ? c : 4;
-  }();
-  return v;
-}
-
-bool hub_inlaunch() {
-  if constexpr (!GNPDE_EXPERIMENTS) return true;
-  static const bool v = [] {
-    const char* e = std::getenv("GNPDE_HUB_FIXUP");
-    return !(e && std::atoi(e) == 1);
-  }();
-  return v;
-}
-
-int agg_variant() {
-  if constexpr (!GNPDE_EXPERIMENTS) return 0;
-  static const int v = [] {
-    const char* e = std::getenv("GNPDE_AGG_VARIANT");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-
-}  // namespace gnpde
-
 using namespace gnpde;
 
 extern "C" {

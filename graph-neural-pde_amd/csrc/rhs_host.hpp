@@ -2,8 +2,6 @@
 // translation units (rhs.hip: K1 and the unfused attention pieces;
 // attention.hip: the fused attention RHS).
 #pragma once
-#include <cstdlib>
-
 #include "scores.hpp"
 
 namespace gnpde {
@@ -38,18 +36,6 @@ inline ScoreArgs make_score_args(int mode, int64_t heads, int64_t dk, const doub
   sa.p0 = p0;
   sa.p1 = p1;
   return sa;
-}
-
-// Experiment knob (not part of the ABI contract): GNPDE_XCD_REMAP=1 maps
-// contiguous eighths of the K1 work items to one XCD each; =K (>= 2) deals
-// chunks of K consecutive blocks to the XCDs in turn (common.hpp xcd_block).
-inline int xcd_remap_enabled() {
-  if constexpr (!GNPDE_EXPERIMENTS) return 0;
-  static const int on = [] {
-    const char* e = std::getenv("GNPDE_XCD_REMAP");
-    return e ? std::max(0, std::atoi(e)) : 0;
-  }();
-  return on;
 }
 
 // The stage struct's own consistency (include/gnpde.h, fused solver epilogue).
@@ -93,7 +79,6 @@ inline int check_stage(const gnpde_stage_epilogue_t& st) {
 inline Epi make_epi(const float* x, int64_t ldx, const float* x0, int64_t ldx0, const float* alpha, const float* beta,
                     int flags, float* f, int64_t ldf, const gnpde_stage_epilogue_t* stage = nullptr) {
   Epi e{};
-  e.xcd_remap = xcd_remap_enabled();
   e.has_stage = stage != nullptr;
   if (stage) e.st = *stage;
   e.x = x;
@@ -132,17 +117,8 @@ inline int check_epi(const Epi& e, int64_t C, int64_t n_heavy, const void* parti
 
 // team geometry for the per-edge modes: VEC = 4, S = dk/4, T = H*S, both powers
 // of two, T <= 64; otherwise lane mode (T = 0).
-inline bool team_mode_enabled() {  // GNPDE_TEAM=0 forces lane mode (diagnostics)
-  static const bool on = [] {
-    const char* e = std::getenv("GNPDE_TEAM");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 inline Team team_geometry(const ScoreArgs& sa) {
   Team tm{0, 0};
-  if (!team_mode_enabled()) return tm;
   if (sa.mode != GNPDE_SCORE_DOT && sa.mode != GNPDE_SCORE_EXP_KERNEL && sa.mode != GNPDE_SCORE_COSINE &&
       sa.mode != GNPDE_SCORE_PEARSON)
     return tm;

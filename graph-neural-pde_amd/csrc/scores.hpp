@@ -55,24 +55,12 @@ __device__ __forceinline__ float pair_score(int mode, const float* __restrict__ 
 // basic blocks between a wave's gathers and their uses — behind branches the
 // compiler issued each score load just before its push (the 8-head long items of
 // the Cora-sized CSC statistics waited out one load latency per push).
-#ifndef GNPDE_PUSH_SELECT
-#define GNPDE_PUSH_SELECT 1
-#endif
 __device__ __forceinline__ void online_push(double& M, float& L, double s) {
-  if constexpr (GNPDE_PUSH_SELECT) {
-    const bool gt = s > M;
-    const float e = expf((float)(gt ? M - s : s - M));
-    const float up = (M == -INFINITY ? 0.f : L * e) + 1.f;
-    L = gt ? up : L + e;
-    M = gt ? s : M;
-    return;
-  }
-  if (s > M) {
-    L = (M == -INFINITY ? 0.f : L * expf((float)(M - s))) + 1.f;
-    M = s;
-  } else {
-    L += expf((float)(s - M));
-  }
+  const bool gt = s > M;
+  const float e = expf((float)(gt ? M - s : s - M));
+  const float up = (M == -INFINITY ? 0.f : L * e) + 1.f;
+  L = gt ? up : L + e;
+  M = gt ? s : M;
 }
 
 __device__ __forceinline__ void online_merge(double& M, float& L, double M2, float L2) {
@@ -199,17 +187,10 @@ __device__ __forceinline__ void lanes_merge(double (&M)[MAXH], float (&L)[MAXH])
 // its chunks in one round and the heads' xor trees interleave — the same merges in
 // the same order per head, so the same bits.  (A hub group's merge ran head after
 // head, a load and a 6-step tree each: serial latency at 8 heads.)
-#ifndef GNPDE_MERGE_ALL_HEADS
-#define GNPDE_MERGE_ALL_HEADS 1
-#endif
 template <int MAXH>
 __device__ __forceinline__ void stats_merge_store_heads(int g, int first, int nch, int H,
                                                         const double* __restrict__ partials, double* __restrict__ m_out,
                                                         float* __restrict__ rl_out, float* __restrict__ mr_out) {
-  if constexpr (!GNPDE_MERGE_ALL_HEADS) {
-    for (int h = 0; h < H; ++h) stats_merge_store(g, first, nch, H, h, partials, m_out, rl_out, mr_out);
-    return;
-  }
   const int lane = threadIdx.x & 63;
   double M[MAXH];
   float L[MAXH];

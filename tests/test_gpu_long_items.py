@@ -606,7 +606,7 @@ def flash(g, x, x0, proj, h, norm_idx, fuse_direct=True):
 @pytest.mark.parametrize("norm_idx", [0, 1])
 @pytest.mark.parametrize("C,h,att", FLASH_SHAPES)
 def test_flash_rhs_on_long_items(world, C, h, att, norm_idx, B):
-    """ops.attn_dot_rhs (dot_agg / dot_agg1 / dot_dst_agg / dot_dst_agg1 kernels): the online-softmax
+    """ops.attn_dot_rhs (dot_agg / dot_agg1 / dot_dst_agg kernels): the online-softmax
     running maximum carried over 256 edges of a row and across hub chunks."""
     assert _lib.fn("gnpde_attn_dot_supported")(h, att // h, C)
     host = world.host

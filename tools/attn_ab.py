@@ -5,7 +5,7 @@ and in the user numbering.  Run once per library (GNPDE_LIB=... for a variant):
 
   tools/attn_ab.py [--tag NAME] [--modes reference:1,per_edge:0,per_edge:1] [--reps 50]
 
-(--modes defaults to $ATT_MODES when set: tools/variants_ab.sh, tools/lin_check.sh.)
+(--modes defaults to $ATT_MODES when set: tools/lin_check.sh.)
 """
 import argparse
 import json

@@ -32,8 +32,8 @@ def main():
     qa, kb = ops.linear(x, W, b, split=Nout // 2)
     ref = (x.double() @ W.double().t() + b.double())
     err = float((torch.cat([qa, kb], 1).double() - ref).abs().max() / ref.abs().max())
-    print(json.dumps({"R": R, "K": K, "Nout": Nout, "us": round(us, 2), "waves": os.environ.get("GNPDE_LIN_WAVES", "2048"),
-                      "variant": os.environ.get("GNPDE_LINEAR", "0"), "TFLOPs": round(2 * R * K * Nout / us / 1e6, 1),
+    print(json.dumps({"R": R, "K": K, "Nout": Nout, "us": round(us, 2),
+                      "TFLOPs": round(2 * R * K * Nout / us / 1e6, 1),
                       "GBs": round((4 * R * K + 4 * R * Nout) / us / 1e3, 1), "rel_err": err}))
 
 

@@ -51,8 +51,7 @@ def main():
             ms = step_ms(func, x, steps)
             base = ms if base is None else base
             print(json.dumps({"graph": name, "world": world, "cols_per_rank": c, "ms_per_step": round(ms, 4),
-                              "implied_speedup": round(base / ms, 3),
-                              "variant": os.environ.get("GNPDE_AGG_VARIANT", "0")}), flush=True)
+                              "implied_speedup": round(base / ms, 3)}), flush=True)
             del func, x
             torch.cuda.empty_cache()
 
