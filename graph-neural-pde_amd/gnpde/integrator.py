@@ -743,7 +743,11 @@ def _host_grid(t_h, dtype, step_size):
     return g
 
 
-def odeint_fixed(func, y0, t, method, step_size=None, combine=None, graph=None):
+def odeint_fixed(func, y0, t, method, step_size=None, combine=None, graph=None, step_hook=None):
+    """``step_hook(y1, t1, layout)`` (the early-stop integrator's score): called after every grid
+    step with the state it produced, in the numbering ``layout`` (None: the caller's); the
+    steps are then driven one at a time — the same launches and replayed one-step graphs,
+    the same bits, nothing read by the host in between.  None: the plain solve."""
     combine = combine or _Combine()
     t_h = _host_times(t)
     grid_h = _host_grid(t_h, t.dtype, step_size)
@@ -756,16 +760,18 @@ def odeint_fixed(func, y0, t, method, step_size=None, combine=None, graph=None):
             C = y0.shape[-1]
             yp = torch.zeros(*y0.shape[:-1], cp, dtype=y0.dtype, device=y0.device)
             yp[..., :C] = y0
-            out = _solve_fused(func, yp, t_h, steps, method, graph)
+            out = _solve_fused(func, yp, t_h, steps, method, graph, step_hook)
             return out[..., :C].contiguous()
-        return _solve_fused(func, y0, t_h, steps, method, graph)
-    if _fused_backward_ok(func, y0, combine, grid_h, t_h) and _nfe_headroom(func, len(steps) * RHS_PER_STEP[method]):
+        return _solve_fused(func, y0, t_h, steps, method, graph, step_hook)
+    if step_hook is None and _fused_backward_ok(func, y0, combine, grid_h, t_h) and _nfe_headroom(func, len(steps) * RHS_PER_STEP[method]):
         return _LaplacianFixedGridFn.apply(y0, func.alpha_train, func.beta_train, func, method, steps, t_h)
     solution = [y0]
     j = 1
     yc = y0
     for ta, tb in steps:
         y1 = _fixed_step(method, func, ta, tb - ta, tb, yc, combine)
+        if step_hook is not None:
+            step_hook(y1, tb, None)
         while j < len(t_h) and tb >= t_h[j]:
             solution.append(_linear_interp(ta, tb, yc, y1, t_h[j]))
             j += 1
@@ -776,7 +782,7 @@ def odeint_fixed(func, y0, t, method, step_size=None, combine=None, graph=None):
     return torch.stack(solution, 0)
 
 
-def _solve_fused(func, y0, t_h, steps, method, graph):
+def _solve_fused(func, y0, t_h, steps, method, graph, step_hook=None):
     """A fixed-grid solve whose RHS emits the stage combinations itself (gnpde
     ODEFuncs, no autograd), in the graph's node numbering when the module offers
     one (ops.NodeLayout: bit-identical results).
@@ -818,6 +824,9 @@ def _solve_fused(func, y0, t_h, steps, method, graph):
         p = 0      # the state is in bufs[p]
         i = 0      # next step to run
         j = 1      # next output time
+        if step_hook is not None:
+            _hooked_steps(func, method, steps, t_h, sol, lay, pool, sg, inplace, step_hook)
+            j = len(t_h)
         while j < len(t_h):
             if i >= n:  # a degenerate grid (t0 == t1): the state itself
                 _to_user(bufs[p], sol[j], lay)
@@ -848,6 +857,34 @@ def _solve_fused(func, y0, t_h, steps, method, graph):
     finally:
         func._layout = None
     return sol
+
+
+def _hooked_steps(func, method, steps, t_h, sol, lay, pool, sg, inplace, step_hook):
+    """_solve_fused's loop with ``step_hook`` after every grid step: one _advance per step (a
+    replayed one-step graph once warm), the hook's launch behind it on the stream.  The
+    last step stores the result in the caller's numbering as the plain solve does, and the
+    hook sees that slice (layout None)."""
+    bufs, ws = pool.bufs, pool.ws
+    n = len(steps)
+    p, j = 0, 1
+    for m, (ta, tb) in enumerate(steps):
+        if m == n - 1 and j == len(t_h) - 1 and t_h[j] == tb:
+            _fused_step(method, func, ta, tb - ta, tb, bufs[p], ws, out=sol[j],
+                        out_rows=lay.order32 if lay is not None else None, inplace=inplace)
+            step_hook(sol[j], tb, None)
+            return
+        inside = j < len(t_h) and tb >= t_h[j] and t_h[j] != tb  # interpolated from the step's input
+        p = _advance(func, method, steps, m, m + 1, p, pool, sg, inplace and not inside)
+        step_hook(bufs[p], tb, lay)
+        while j < len(t_h) and tb >= t_h[j]:
+            if t_h[j] == tb:
+                _to_user(bufs[p], sol[j], lay)
+            else:
+                _to_user(_linear_interp(ta, tb, bufs[1 - p], bufs[p], t_h[j]), sol[j], lay)
+            j += 1
+    while j < len(t_h):  # a degenerate grid (t0 == t1): the state itself
+        _to_user(bufs[p], sol[j], lay)
+        j += 1
 
 
 def _advance(func, method, steps, i, m, p, pool, sg, inplace=False):
@@ -896,7 +933,7 @@ class _RKAdaptive(object):
     explicit embedded tableau (dopri5, bosh3, fehlberg2, adaptive_heun)."""
 
     def __init__(self, func, y0, rtol, atol, combine, method='dopri5', first_step=None, safety=0.9, ifactor=10.0,
-                 dfactor=0.2, max_num_steps=2 ** 31 - 1, norm=_rms_norm):
+                 dfactor=0.2, max_num_steps=2 ** 31 - 1, norm=_rms_norm, accept_hook=None, max_attempts=None):
         (self.order, self.alpha, self.beta, self.c_sol, self.c_error, self.c_mid) = _TABLEAUS[method]
         # FSAL tableaus (dopri5, bosh3): c_sol == beta[-1] and c_sol[-1] == 0, so y1 is the last stage input
         self.fsal = self.c_sol[-1] == 0 and list(self.c_sol[:-1]) == list(self.beta[-1])
@@ -912,6 +949,13 @@ class _RKAdaptive(object):
         self._dev = dev
         self.max_num_steps = max_num_steps
         self.n_steps = 0
+        # The early-stop integrator's additions (inert when None).  accept_hook(y1, t1, layout):
+        # called after every accepted step with the buffer that holds y1.  max_attempts: the
+        # solve stops after that many attempts, rejected ones included (src/early_stop_solver.py:
+        # 77-88), and returns the state at the last accepted t1 (y0 if none) for every output
+        # time not reached — where max_num_steps raises.
+        self.accept_hook, self.max_attempts = accept_hook, max_attempts
+        self.capped = False
 
     def _scalar_tensor(self, name):
         v = self._tensors.get(name)
@@ -1007,6 +1051,9 @@ class _RKAdaptive(object):
         for i in range(1, len(t)):
             next_t = t[i]
             while next_t > t_cur:
+                if self.max_attempts is not None and self.n_steps >= self.max_attempts:
+                    self.capped = True
+                    break
                 check_step(t_cur, dt, self.n_steps, self.max_num_steps)
                 y1, f1, y1_err, k = self._step(y, f, t_cur, dt)
                 error_tol = self.atol + self.rtol * torch.max(y.abs(), y1.abs())
@@ -1015,9 +1062,11 @@ class _RKAdaptive(object):
                     last = (y, y1, k, dt)
                     t_prev, t_cur = t_cur, t_cur + dt
                     y, f = y1, f1
+                    if self.accept_hook is not None:
+                        self.accept_hook(y, float(t_cur), None)
                 dt = self._optimal_step_size(dt, error_ratio)
                 self.n_steps += 1
-            if last is None or next_t == t_cur:
+            if self.capped or last is None or next_t == t_cur:
                 solution.append(y)
             else:
                 y_prev, y_cur, k, dts = last
@@ -1583,9 +1632,13 @@ class _RKAdaptiveFused(_RKAdaptive):
             if spec_ok and th[-1] > th[0]:  # the first step runs while the host waits for its size
                 pending = self._rec_reader(st, self._run_step(st, graphs_ok, t_cur, 0.0, True))
             dt = dt_read()[2]
+        cap, hook = self.max_attempts, self.accept_hook
         for i_out in range(1, len(th)):
             next_t = th[i_out]
             while next_t > t_cur:
+                if cap is not None and self.n_steps >= cap:
+                    self.capped = True
+                    break
                 check_step(t_cur, dt, self.n_steps, self.max_num_steps)
                 mid = t_cur + dt >= next_t  # an accepted step would cross an output time: keep the dense-output k's
                 if pending is not None:
@@ -1599,7 +1652,7 @@ class _RKAdaptiveFused(_RKAdaptive):
                 # ahead only after a step whose k's the dense output does not need (the step ahead
                 # overwrites them); it keeps its own (mid variant: its dt is not known yet)
                 if spec_ok and st.warm and not mid and self.n_steps + 1 < self.max_num_steps and \
-                        _nfe_headroom(self.func, 2 * P.ns):
+                        (cap is None or self.n_steps + 1 < cap) and _nfe_headroom(self.func, 2 * P.ns):
                     rotate(bufs, P, 1)
                     ahead = self._rec_reader(st, self._run_step(st, graphs_ok, t_cur + dt, dt, True))
                 # the step crossing next_t (steps-ahead mode, its k's kept): its dense output is
@@ -1628,6 +1681,10 @@ class _RKAdaptiveFused(_RKAdaptive):
                         pending = ahead  # already on the accepted binding
                     else:
                         rotate(bufs, P, 1)
+                    if hook is not None:
+                        # bufs['Y'] holds y1 now; a step enqueued ahead only reads it, and the hook's
+                        # launch follows that step on the stream: no copy, no synchronisation
+                        hook(bufs['Y'], t_cur, lay)
                 elif ahead is not None:  # rejected: discard the step ahead, step n again from its inputs
                     rotate(bufs, P, -1)
                     st.dt.fill_(dt_next)
@@ -1639,7 +1696,14 @@ class _RKAdaptiveFused(_RKAdaptive):
                     dt_next = next_dt(dt, ratio, float(P.order), self.safety_f, self.ifactor_f, self.dfactor_f)
                 dt = dt_next
                 self.n_steps += 1
-            if next_t == t_cur or last is None:
+            if self.capped and pending is not None:
+                # (a cap below one attempt: the first step, enqueued while its size was read, is dropped)
+                pending = None
+                if hasattr(self.func, 'nfe'):
+                    self.func.nfe -= P.ns
+            if next_t == t_cur or last is None or self.capped:
+                # (capped: the state at the last accepted t1, written after anything a folded or
+                # pre-enqueued dense output of a rejected step left in this slice)
                 if self.host:
                     sol[i_out].copy_(bufs['Y'])
                 else:
@@ -1713,14 +1777,18 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, combine
     if t.dim() != 1 or len(t) < 2:
         raise ValueError("t must be a 1-D tensor with at least two time points")
     if method in FIXED_METHODS:
-        return odeint_fixed(func, y0, t, method, options.get('step_size'), combine, graph=options.get('gnpde_graph'))
+        return odeint_fixed(func, y0, t, method, options.get('step_size'), combine, graph=options.get('gnpde_graph'),
+                            step_hook=options.get('gnpde_accept_hook'))
     if method in ADAPTIVE_METHODS:
         kw = dict(method=method, first_step=options.get('first_step'),
                   max_num_steps=options.get('max_num_steps', 2 ** 31 - 1), norm=options.get('norm', _rms_norm))
+        hooked = options.get('gnpde_accept_hook') is not None or options.get('gnpde_max_attempts') is not None
+        if hooked:  # the early-stop integrator (gnpde.early_stop_solver); plain solves pass neither
+            kw.update(accept_hook=options.get('gnpde_accept_hook'), max_attempts=options.get('gnpde_max_attempts'))
         if _fused_adaptive_ok(func, y0, combine, options):
             solver = _RKAdaptiveFused(func, y0, rtol, atol, combine, options=options, **kw)
             odeint.last_path = 'fused_krylov' if solver.krylov is not None else 'fused_stage'
-        elif _adaptive_backprop_ok(func, y0, combine, options):
+        elif not hooked and _adaptive_backprop_ok(func, y0, combine, options):
             # backprop through the adaptive solve of the Laplacian as one node (gnpde.adaptive_backprop)
             w, _ = func._weights_tensor()
             out = _LaplacianAdaptiveFn.apply(y0, func.alpha_train, func.beta_train, w, func, _host_times(t), method,
@@ -1733,6 +1801,7 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, combine
             odeint.last_path = 'restated'
         out = solver.integrate(t)
         odeint.last_n_steps = solver.n_steps
+        odeint.last_capped = solver.capped
         odeint.last_dense_fold = bool(getattr(solver, 'fold', False))
         return out
     raise NotImplementedError("gnpde.odeint: method %r not supported (supported: %s)" %
@@ -1741,6 +1810,7 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, combine
 
 odeint.last_n_steps = 0
 odeint.last_path = None  # the last adaptive solve's loop: 'fused_krylov', 'fused_stage' or 'restated'
+odeint.last_capped = False  # whether it stopped at options['gnpde_max_attempts'] before the output time
 odeint.last_dense_fold = False  # whether its dense output was folded into the steps (DENSE_FOLD)
 
 

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._cache import _tensor_key
 
 # hub-splitting threshold (edges per K1 work item).  With the longest-first item
 # order below, full-bench A/B on G-arxiv: 128 -> 8,048-8,200, 256 -> 8,485-8,496,
@@ -2059,4 +2060,110 @@ def rk_combine(y0, ks, coefs, scale, out=None):
         cf[j] = float(c)
     _lib.call("gnpde_rk_combine_f32", ref.numel(), _ptr(y0), nk, kp, cf, float(scale), _ptr(out),
               _stream(ref.device))
+    return out
+
+
+# --------------------------------------------------------------------------- early-stop scoring
+def decode_score_torch(y, W, b, split, label, counts_out, ld=None, rows=None, pred_out=None):
+    """gnpde_decode_score_f32 restated in torch ops (any device, no host read): the path
+    for a decoder outside the kernel's range (K > 128 or Cd > 512) and the scorer the
+    host tests inject.  Same contract: relu of the first Cd columns, the linear layer,
+    argmax with the lowest class winning a tie, the hits of each split ADDED to
+    counts_out[3]."""
+    ld = y.shape[-1] if ld is None else int(ld)
+    K, Cd = W.shape
+    z = torch.relu(y.reshape(-1, ld)[:, :Cd].float())
+    logits = z @ W.float().t()
+    if b is not None:
+        logits = logits + b.float()
+    # the first maximal class (torch.max's index among ties is unspecified on a device)
+    top = logits.max(dim=1, keepdim=True).values
+    ids = torch.arange(K, device=y.device).expand_as(logits)
+    pred = torch.where(logits == top, ids, torch.full_like(ids, K)).min(dim=1).values
+    if rows is not None:
+        r = rows.long()
+        split, label = split[r], label[r]
+    scored = split != 0
+    hit = (pred == label.long()) & scored
+    s = split.to(torch.int32)
+    bits = torch.stack([(s >> k) & 1 for k in range(3)], 1)
+    counts_out += (bits * hit.to(torch.int32).unsqueeze(1)).sum(0).to(counts_out.dtype)
+    if pred_out is not None:
+        pred_out.copy_(torch.where(scored, pred, torch.full_like(pred, -1)).to(pred_out.dtype))
+    return counts_out
+
+
+def decode_score(y, W, b, split, label, counts_out, ld=None, rows=None, pred_out=None):
+    """gnpde_decode_score_f32: score one state against the packed splits (pack_splits) in
+    one launch.  y [..., ld] fp32 (R rows), W [K, Cd] with Cd <= ld, b [K] or None; split
+    uint8 [R] (bit 0 train, 1 validation, 2 test), label int32 [R]; rows int32 [R] or None
+    (state row i takes split / label from position rows[i]: NodeLayout.order32); the
+    three hit counts are ADDED to counts_out (int32 [3], e.g. one slot of a per-solve
+    record); pred_out int32 [R] or None (-1: unscored row).  A decoder outside the
+    kernel's range (GNPDE_EUNSUPPORTED) takes decode_score_torch."""
+    _require_gpu(y, "y", torch.float32)
+    if not y.is_contiguous():
+        raise ValueError("decode_score: y must be contiguous")
+    ld = y.shape[-1] if ld is None else int(ld)
+    R = y.numel() // max(ld, 1)
+    _require_gpu(W, "W", torch.float32)
+    _require_gpu(split, "split", torch.uint8)
+    _require_gpu(label, "label", torch.int32)
+    _require_gpu(counts_out, "counts_out", torch.int32)
+    if W.dim() != 2 or not W.is_contiguous():
+        raise ValueError("decode_score: W must be a contiguous [K, Cd] matrix")
+    K, Cd = W.shape
+    if b is not None:
+        _require_gpu(b, "b", torch.float32)
+        if b.numel() != K or not b.is_contiguous():
+            raise ValueError("decode_score: b must hold K contiguous entries")
+    if split.numel() != R or label.numel() != R or not (split.is_contiguous() and label.is_contiguous()):
+        raise ValueError("decode_score: split and label must hold one contiguous entry per state row (%d)" % R)
+    if counts_out.numel() != 3 or not counts_out.is_contiguous():
+        raise ValueError("decode_score: counts_out must be 3 contiguous int32")
+    for t, nm in ((rows, "rows"), (pred_out, "pred_out")):
+        if t is not None:
+            _require_gpu(t, nm, torch.int32)
+            if t.numel() != R or not t.is_contiguous():
+                raise ValueError("decode_score: %s must hold one contiguous int32 per state row (%d)" % (nm, R))
+    rc = _lib.call_rc("gnpde_decode_score_f32", _ptr(y), R, ld, Cd, _ptr(W), _ptr(b), K, _ptr(split), _ptr(label),
+                      _ptr(rows), _ptr(counts_out), _ptr(pred_out), _stream(y.device))
+    if rc == _lib.EUNSUPPORTED:
+        return decode_score_torch(y, W, b, split, label, counts_out, ld=ld, rows=rows, pred_out=pred_out)
+    _lib.check(rc, "gnpde_decode_score_f32")
+    return counts_out
+
+
+_SPLITS = {}  # (tensor keys of y and the masks, R, device) -> (split, label, sizes)
+
+
+def pack_splits(data, R, device):
+    """The packed split masks and labels of a data object, once per object: split uint8 [R]
+    (bit 0 ``train_mask``, bit 1 ``val_mask``, bit 2 ``test_mask``), label int32 [R]
+    (``data.y``) and the three mask sizes as host ints (read here, once).  The tensors are
+    [N] or [B, N], flattened to rows; a per-node set repeats over the batch elements of
+    a [B, N] state.  Cached by tensor identity and version."""
+    srcs = (data.y, data.train_mask, data.val_mask, data.test_mask)
+    key = tuple(_tensor_key(t) for t in srcs) + (int(R), str(device))
+    hit = _SPLITS.get(key)
+    if hit is not None:
+        return hit
+
+    def rows(t):
+        t = t.reshape(-1)
+        if t.numel() != R:
+            if t.numel() == 0 or R % t.numel() != 0:
+                raise ValueError("pack_splits: %d entries do not tile %d state rows" % (t.numel(), R))
+            t = t.repeat(R // t.numel())
+        return t
+
+    masks = [rows(m).to(torch.bool) for m in srcs[1:]]
+    split = torch.zeros(R, dtype=torch.uint8, device=masks[0].device)
+    for k, m in enumerate(masks):
+        split |= m.to(torch.uint8) << k
+    sizes = tuple(int(v) for v in torch.stack([m.sum() for m in masks]).tolist())
+    out = (split.to(device).contiguous(), rows(data.y).to(device=device, dtype=torch.int32).contiguous(), sizes)
+    if len(_SPLITS) >= 8:
+        _SPLITS.clear()
+    _SPLITS[key] = out
     return out

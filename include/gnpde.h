@@ -658,6 +658,26 @@ int gnpde_rk_combine_f32(int64_t n, const float* y0, int nk, const float* const*
 int gnpde_rows_copy(const void* src, int64_t rows, int64_t row_bytes, const int64_t* order, void* dst,
                     void* dst_copy, void* stream);
 
+/* The early-stop test integrator's score of one state (gnpde.early_stop_solver;
+ * src/early_stop_solver.py:108-128): for every row r < R of y [R, ld] whose split
+ * mask is non-zero,
+ *   z = relu(y[r, 0:Cd]),  logit[c] = b[c] + sum_j W[c, j] z[j]   (W [K, Cd] row-major,
+ *   fp32 fused multiply-adds, j ascending; b NULL = 0),  pred = argmax_c logit[c]
+ *   (the lowest class wins a tie),
+ * and each set bit of the row's mask (bit 0 train, bit 1 validation, bit 2 test)
+ * adds 1 to counts[bit] when pred equals the row's label.  counts[3] is ADDED to
+ * (integer atomics): the caller zeroes it, or aims it at a slot of a per-solve
+ * record.  rows (may be NULL = identity): state row r takes its mask and label from
+ * split[rows[r]], label[rows[r]] (a state kept in a node renumbering; an entry
+ * outside [0, R) leaves the row unscored).  pred_out (may be NULL): pred of state row
+ * r, -1 for an unscored row.  A row with mask 0 is not read.  Cd <= ld (an augmented
+ * state is scored on its first half).  One launch, no workspace, no host read.
+ * GNPDE_EINVAL: K < 1, Cd < 1, Cd > ld, R < 0, a NULL required pointer;
+ * GNPDE_EUNSUPPORTED: K > 128 or Cd > 512.                                   */
+int gnpde_decode_score_f32(const float* y, int64_t R, int64_t ld, int64_t Cd, const float* W, const float* b,
+                           int64_t K, const uint8_t* split, const int32_t* label, const int32_t* rows,
+                           int32_t* counts, int32_t* pred_out, void* stream);
+
 /* <a, b> of two fp32 arrays in fp64 (n elements), written to *out on the device:
  * the parameter gradients of the RHS backward, d alpha_train = sigma'(alpha)
  * <gf, A x - x> and d beta_train = <gf, x0> (torch autograd of
