@@ -167,6 +167,8 @@ SIGNATURES = {
     "gnpde_squareplus_backward_workspace_bytes": (_size, [_i64]),
     "gnpde_squareplus_backward_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _size,
                                              _vp]),
+    "gnpde_knn_workspace_bytes": (_size, [_i64, _i64]),
+    "gnpde_knn_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 
 # constants mirrored from include/gnpde.h

@@ -2167,3 +2167,110 @@ def pack_splits(data, R, device):
         _SPLITS.clear()
     _SPLITS[key] = out
     return out
+
+
+# --------------------------------------------------------------------------- kNN rewiring
+KNN_MAX_K = 64  # the kernel's range (csrc/knn.hip kKnnMaxK); a larger k takes knn_torch
+KNN_TORCH_BYTES = 1 << 28  # knn_torch: bytes of one chunk's [rows, N, C] differences
+
+
+def _knn_input(x, name):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("%s: x must be a torch.Tensor" % name)
+    if x.dtype != torch.float32:
+        raise TypeError("gnpde: %s: x must be torch.float32, got %s" % (name, x.dtype))
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    if x.dim() != 3 or x.shape[-1] < 1:
+        raise ValueError("%s: x must be [B, N, C] or [N, C] with C >= 1, got %s" % (name, tuple(x.shape)))
+    return x
+
+
+def knn_mask(x):
+    """The masked rows of x [B, N, C] (bool [B, N]): all zero, or any non-finite value."""
+    return (x == 0).all(dim=-1) | ~torch.isfinite(x).all(dim=-1)
+
+
+def knn_torch(x, k, return_dist=False, chunk_bytes=None):
+    """gnpde_knn_f32 restated in torch ops (any device; chunked over query rows): the path
+    for k > 64, the function the host tests inject and the baseline of tools/knn_bench.py.
+    Same contract as knn: difference-form fp32 distances, the k smallest (d, j) keys in
+    ascending order (one integer key (float bits of d) << 32 | j per pair, so the order
+    does not depend on topk's tie behaviour), masked rows as in knn.  A graph with fewer
+    than k unmasked rows pads with index -1 / distance +inf (k > N raises).  chunk_bytes:
+    the size of one chunk's [rows, N, C] differences (KNN_TORCH_BYTES)."""
+    x = _knn_input(x, "knn_torch")
+    k = int(k)
+    B, N, C = x.shape
+    if k < 1:
+        raise ValueError("knn_torch: k=%d must be >= 1" % k)
+    if k > N:
+        raise ValueError("knn_torch: k=%d exceeds the %d rows of a graph" % (k, N))
+    dev = x.device
+    masked = knn_mask(x)
+    n_valid = (~masked).sum(dim=1).to(torch.int32)
+    xs = torch.where(masked.unsqueeze(-1), torch.zeros_like(x), x)  # keep non-finite values out of the arithmetic
+    idx = torch.empty(B, N, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(B, N, k, dtype=torch.float32, device=dev) if return_dist else None
+    j = torch.arange(N, dtype=torch.int64, device=dev)
+    none = torch.iinfo(torch.int64).max
+    rows = max(1, min(N, int(chunk_bytes or KNN_TORCH_BYTES) // max(1, 4 * N * C)))
+    for b in range(B):
+        for r0 in range(0, N, rows):
+            r1 = min(N, r0 + rows)
+            d = ((xs[b, r0:r1, None, :] - xs[b, None, :, :]) ** 2).sum(-1)          # [rows, N], d >= 0
+            key = (d.view(torch.int32).to(torch.int64) << 32) | j                    # order of (d, j)
+            key = torch.where(masked[b].unsqueeze(0), torch.full_like(key, none), key)
+            top = torch.topk(key, k, dim=1, largest=False, sorted=True).values
+            pad = top == none
+            idx[b, r0:r1] = torch.where(pad, torch.full_like(top, -1), top & 0xFFFFFFFF).to(torch.int32)
+            if return_dist:
+                dd = (top >> 32).to(torch.int32).view(torch.float32)
+                dist[b, r0:r1] = torch.where(pad, torch.full_like(dd, float("inf")), dd)
+        own = torch.arange(N, dtype=torch.int32, device=dev).unsqueeze(1).expand(N, k)
+        idx[b] = torch.where(masked[b].unsqueeze(1), own, idx[b])
+        if return_dist:
+            dist[b] = torch.where(masked[b].unsqueeze(1), torch.zeros_like(dist[b]), dist[b])
+    return (idx, dist, n_valid) if return_dist else (idx, n_valid)
+
+
+def knn(x, k, return_dist=False):
+    """gnpde_knn_f32: the k nearest rows of every row of x [B, N, C] (or [N, C]: B = 1)
+    within its graph, by d_ij = sum_c (x_ic - x_jc)^2 in fp32, in ascending (d_ij, j).
+    Returns (idx int32 [B, N, k], n_valid int32 [B]) or (idx, dist fp32 [B, N, k],
+    n_valid); nothing is read back here (n_valid stays on the device).  A masked row
+    (all zero, or any non-finite value) is never a neighbour and returns its own index;
+    a graph with n_valid < k pads with -1 / +inf (k > N raises).  A column prefix of a
+    wider buffer: knn_strided.  k > 64 (outside the kernel's range) takes knn_torch."""
+    return _knn(x, k, return_dist, None)
+
+
+def knn_strided(buf, cols, k, return_dist=False):
+    """knn on the first ``cols`` columns of a contiguous [B, N, ld] (or [N, ld]) buffer,
+    without a copy (gnpde_knn_f32's ld > C)."""
+    return _knn(buf, k, return_dist, int(cols))
+
+
+def _knn(x, k, return_dist, cols):
+    x = _knn_input(x, "knn")
+    _require_gpu(x, "x", torch.float32)
+    x = x.contiguous()
+    k = int(k)
+    B, N, ld = x.shape
+    C = ld if cols is None else cols
+    if not 1 <= C <= ld:
+        raise ValueError("knn: cols=%d must be in [1, %d]" % (C, ld))
+    if k < 1:
+        raise ValueError("knn: k=%d must be >= 1" % k)
+    if k > N:
+        raise ValueError("knn: k=%d exceeds the %d rows of a graph" % (k, N))
+    if k > KNN_MAX_K:
+        return knn_torch(x[..., :C], k, return_dist)
+    dev = x.device
+    idx = torch.empty(B, N, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(B, N, k, dtype=torch.float32, device=dev) if return_dist else None
+    n_valid = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(_lib.fn("gnpde_knn_workspace_bytes")(B, N)), dtype=torch.uint8, device=dev)
+    _lib.call("gnpde_knn_f32", _ptr(x), B, N, C, ld, k, _ptr(idx), _ptr(dist), _ptr(n_valid), _ptr(ws),
+              _stream(dev))
+    return (idx, dist, n_valid) if return_dist else (idx, n_valid)

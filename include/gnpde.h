@@ -927,6 +927,21 @@ int gnpde_squareplus_backward_f32(const int32_t* rowptr, const int32_t* perm, in
                                   const int64_t* amax, float* gs, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
+/* Exact k nearest neighbours of the rows of x [B, N, C] (row stride ld) within each graph, by
+ * the squared distance d_ij = sum_c (x_ic - x_jc)^2 in fp32 (the difference form; the self
+ * index is a candidate, d_ii = 0), in ascending (d_ij, j): the kNN rewiring of
+ * src/graph_rewiring.py:122-161 (an entry point added under ABI 8).  A row that is all
+ * zero or holds a non-finite value is masked: never a candidate, and as a query it
+ * returns its own index k times (distance 0).  idx_out [B, N, k] holds per-graph indices
+ * in [0, N); dist_out [B, N, k] (or NULL) the distances; n_valid [B] the unmasked rows of
+ * each graph, written by the mask pre-pass (a graph with n_valid < k pads its rows with
+ * index -1 / distance +inf).  workspace: gnpde_knn_workspace_bytes(B, N) bytes (the row
+ * masks).  1 <= k <= 64, else GNPDE_EUNSUPPORTED.  Everything is enqueued on the stream;
+ * the result does not depend on the launch geometry.                                   */
+size_t gnpde_knn_workspace_bytes(int64_t B, int64_t N);
+int gnpde_knn_f32(const float* x, int64_t B, int64_t N, int64_t C, int64_t ld, int64_t k, int32_t* idx_out,
+                  float* dist_out, int32_t* n_valid, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
