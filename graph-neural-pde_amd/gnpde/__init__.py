@@ -13,6 +13,7 @@ from .block_transformer_hard_attention import HardAttODEblock  # noqa: F401
 from .block_transformer_attention import AttODEblock  # noqa: F401
 from .function_GAT_attention import ODEFuncAtt, SpGraphAttentionLayer  # noqa: F401
 from .function_laplacian_diffusion import LaplacianODEFunc  # noqa: F401
+from .function_laplacian_multimodal import MultiModalLaplacianODEFunc  # noqa: F401
 from .function_transformer_attention import ODEFuncTransformerAtt, SpGraphTransAttentionLayer  # noqa: F401
 from .model_configurations import set_block, set_function  # noqa: F401
 from .integrator import odeint  # noqa: F401

@@ -169,6 +169,7 @@ SIGNATURES = {
                                              _vp]),
     "gnpde_knn_workspace_bytes": (_size, [_i64, _i64]),
     "gnpde_knn_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "gnpde_cross_attention_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _vp]),
 }
 
 # constants mirrored from include/gnpde.h

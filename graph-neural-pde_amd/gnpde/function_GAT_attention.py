@@ -80,7 +80,8 @@ def _check_supported(opt):
                                   "opt['gnpde_gat_mix_features'] = True to select it")
     if opt.get('multi_modal', False):
         raise NotImplementedError("gnpde: multi_modal is broken in the reference (torch.nn.softmax, "
-                                  "function_GAT_attention.py:121) and out of scope")
+                                  "function_GAT_attention.py:121) and out of scope for the GAT function "
+                                  "(opt['gnpde_multi_modal'] serves function='laplacian' under block='constant' only)")
 
 
 def _needs_grad(*ts):

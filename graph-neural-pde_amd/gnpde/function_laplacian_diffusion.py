@@ -83,8 +83,14 @@ class LaplacianODEFunc(ODEFunc):
         # vector-Jacobian products form no weight gradient (the SDDMM) only to drop it
         self.adjoint_const_weights = False
         if opt.get('multi_modal', False):
+            if opt.get('gnpde_multi_modal', False):
+                raise NotImplementedError("gnpde: multi_modal with opt['gnpde_multi_modal'] is served by "
+                                          "function_laplacian_multimodal.MultiModalLaplacianODEFunc: select the "
+                                          "function with model_configurations.set_function(opt)")
             raise NotImplementedError("gnpde: multi_modal is broken in the reference (torch.nn.softmax, "
-                                      "function_laplacian_diffusion.py:63) and out of scope")
+                                      "function_laplacian_diffusion.py:63); set opt['gnpde_multi_modal'] = True to "
+                                      "run the intended call, torch.softmax(..., dim=-1) "
+                                      "(model_configurations.set_function then returns MultiModalLaplacianODEFunc)")
 
     def _weights_tensor(self):
         blk = self.opt.get('block', 'constant')

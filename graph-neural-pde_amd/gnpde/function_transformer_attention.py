@@ -96,7 +96,9 @@ def _check_supported(opt):
                                   "with a 2-D slice and without num_nodes, :264); set opt['gnpde_square_plus'] = "
                                   "True to run the intended call, utils.squareplus(prods, edge[:, norm_idx, :], None)")
     if opt.get('multi_modal', False):
-        raise NotImplementedError("gnpde: multi_modal is broken in the reference and out of scope")
+        raise NotImplementedError("gnpde: multi_modal is broken in the reference and out of scope for the "
+                                  "transformer function (opt['gnpde_multi_modal'] serves function='laplacian' "
+                                  "under block='constant' only)")
     if opt.get('beltrami', False) and opt.get('attention_type', 'scaled_dot') == 'exp_kernel':
         raise NotImplementedError("gnpde: the beltrami exp_kernel branch slices nodes instead of features in the "
                                   "reference (:166-167) and is not implemented")

@@ -6,7 +6,9 @@ Built here: block 'constant', 'attention', 'mixed',
 (function_GAT_attention.ODEFuncAtt) is returned when the option dict sets
 ``gnpde_gat`` to a true value; without the key it raises NotImplementedError
 naming the key (the plain dict's behaviour is pinned by the host tests until the
-switch becomes the default).  Block 'rewire_attention' is out of scope and raises
+switch becomes the default).  'laplacian' with ``multi_modal`` and
+``gnpde_multi_modal`` both set is function_laplacian_multimodal.MultiModalLaplacianODEFunc
+(the second modality's cross-attention; block 'constant' only).  Block 'rewire_attention' is out of scope and raises
 NotImplementedError naming the reason, rather than silently falling back to a
 different model.
 """
@@ -15,6 +17,7 @@ from .block_mixed import MixedODEblock
 from .block_transformer_hard_attention import HardAttODEblock
 from .block_transformer_attention import AttODEblock
 from .function_laplacian_diffusion import LaplacianODEFunc
+from .function_laplacian_multimodal import MultiModalLaplacianODEFunc
 from .function_GAT_attention import ODEFuncAtt
 from .function_transformer_attention import ODEFuncTransformerAtt
 
@@ -50,6 +53,8 @@ def set_block(opt):
 def set_function(opt):
     ode_str = opt['function']
     if ode_str == 'laplacian':
+        if opt.get('multi_modal', False) and opt.get('gnpde_multi_modal', False):
+            return MultiModalLaplacianODEFunc
         return LaplacianODEFunc
     if ode_str == 'transformer':
         return ODEFuncTransformerAtt

@@ -2274,3 +2274,67 @@ def _knn(x, k, return_dist, cols):
     _lib.call("gnpde_knn_f32", _ptr(x), B, N, C, ld, k, _ptr(idx), _ptr(dist), _ptr(n_valid), _ptr(ws),
               _stream(dev))
     return (idx, dist, n_valid) if return_dist else (idx, n_valid)
+
+
+# --------------------------------------------------------------------------- multi_modal cross-attention
+CROSS_ATTENTION_MAX_C = 256  # the kernel's range (csrc/cross_attention.hip kXaMaxC)
+
+
+def _cross_attention_input(q, k, v, name):
+    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor" % (name, nm))
+        if t.dtype != torch.float32:
+            raise TypeError("gnpde: %s: %s must be torch.float32, got %s" % (name, nm, t.dtype))
+    if q.dim() == 2:
+        q, k, v = q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0)
+    if q.dim() != 3 or k.dim() != 3 or q.shape[-1] < 1:
+        raise ValueError("%s: q must be [B, N, C] and k / v [B, M, C] with C >= 1, got %s / %s / %s"
+                         % (name, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    if k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise ValueError("%s: k %s and v %s must both be [B=%d, M, C=%d]"
+                         % (name, tuple(k.shape), tuple(v.shape), q.shape[0], q.shape[2]))
+    if k.shape[1] < 1:
+        raise ValueError("%s: M = 0 (a softmax over no keys)" % name)
+    return q, k, v
+
+
+def cross_attention_torch(q, k, v, scale, lse=False):
+    """gnpde_cross_attention_f32 restated in torch ops (any device): the function the host
+    tests check against the oracle and the baseline of tools/multimodal_bench.py.  Same
+    contract as cross_attention; it materialises the [B, N, M] scores."""
+    shape = q.shape
+    q, k, v = _cross_attention_input(q, k, v, "cross_attention_torch")
+    s = torch.matmul(q, k.transpose(1, 2)) * float(scale)
+    out = torch.matmul(torch.softmax(s, dim=-1), v).view(shape)
+    if lse:
+        return out, torch.logsumexp(s, dim=-1).view(shape[:-1])
+    return out
+
+
+def cross_attention(q, k, v, scale, lse=False, out=None):
+    """gnpde_cross_attention_f32: out[b,n,:] = softmax_m(scale * <q[b,n], k[b,m]>) v[b,m,:]
+    for q [B, N, C] (or [N, C]: B = 1) and k / v [B, M, C] fp32, flash style on the fp32
+    matrix cores: no [B, N, M] buffer.  lse=True also returns max + ln(sum exp) of the
+    scaled scores per row [B, N] (what the backward recomputes the softmax from).
+    1 <= C <= 256 (a wider C raises: there is no other device path), any N and M >= 1.
+    The same bits on every run."""
+    shape = q.shape
+    q, k, v = _cross_attention_input(q, k, v, "cross_attention")
+    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+        _require_gpu(t, nm, torch.float32)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    B, N, C = q.shape
+    M = k.shape[1]
+    dev = q.device
+    if out is None:
+        out = torch.empty(B, N, C, dtype=torch.float32, device=dev)
+    else:
+        _require_gpu(out, "out", torch.float32)
+        if not out.is_contiguous() or out.numel() != B * N * C:
+            raise ValueError("cross_attention: out must be contiguous and hold %d x %d x %d" % (B, N, C))
+    ls = torch.empty(B, N, dtype=torch.float32, device=dev) if lse else None
+    _lib.call("gnpde_cross_attention_f32", _ptr(q), C, _ptr(k), _ptr(v), B, N, M, C, float(scale), _ptr(out), C,
+              _ptr(ls), _stream(dev))
+    out = out.view(shape)
+    return (out, ls.view(shape[:-1])) if lse else out

@@ -942,6 +942,17 @@ size_t gnpde_knn_workspace_bytes(int64_t B, int64_t N);
 int gnpde_knn_f32(const float* x, int64_t B, int64_t N, int64_t C, int64_t ld, int64_t k, int32_t* idx_out,
                   float* dist_out, int32_t* n_valid, void* workspace, void* stream);
 
+/* Cross-attention of the node rows against a second modality's tokens (multi_modal,
+ * src/function_laplacian_diffusion.py:61-63; an entry point added under ABI 8):
+ *   out[b,n,:] = softmax_m(scale * <q[b,n,:], k[b,m,:]>) v[b,m,:]
+ * q [B, N, C] (row stride ldq), k / v [B, M, C] contiguous, out [B, N, C] (row stride ldo).
+ * Flash style on the fp32 matrix cores (exact fp32 products): the [N, M] scores are never
+ * stored.  lse [B*N] (or NULL) receives max_m + ln(sum_m exp) of the scaled scores, from
+ * which a backward recomputes the softmax.  1 <= C <= 256, else GNPDE_EUNSUPPORTED; any
+ * N >= 0 and M >= 1.  No atomics, a fixed reduction order: the same bits on every run.  */
+int gnpde_cross_attention_f32(const float* q, int64_t ldq, const float* k, const float* v, int64_t B, int64_t N,
+                              int64_t M, int64_t C, float scale, float* out, int64_t ldo, float* lse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
