@@ -18,6 +18,7 @@ STAGE_MAX_K = 6
 STAGE_PRE_K = 2  # operands the fixed-grid epilogues prefetch (csrc/common.hpp kStagePre)
 DENSE_BASIS = 5  # the folded dense output's basis polynomials (ABI 8)
 DENSE_SLOTS = STAGE_MAX_K + 2  # its operand slots: output 0's base, k[0..5], f
+ADAMS_MAX_HISTORY = 11  # GNPDE_ADAMS_MAX_HISTORY: history arrays of one predictor pass
 
 
 class StageOut(ctypes.Structure):
@@ -170,6 +171,11 @@ SIGNATURES = {
     "gnpde_knn_workspace_bytes": (_size, [_i64, _i64]),
     "gnpde_knn_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gnpde_cross_attention_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _vp]),
+    "gnpde_adams_predict_f32": (_int, [_i64, _vp, _int, ctypes.POINTER(_vp), ctypes.POINTER(_f64),
+                                       ctypes.POINTER(_f64), _vp, _vp, _vp, _vp]),
+    "gnpde_adams_workspace_bytes": (_size, []),
+    "gnpde_adams_status_reset": (_int, [_vp, _vp]),
+    "gnpde_adams_correct_f32": (_int, [_i64, _vp, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _size, _vp]),
 }
 
 # constants mirrored from include/gnpde.h

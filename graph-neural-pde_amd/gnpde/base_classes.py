@@ -283,11 +283,18 @@ class ODEblock(nn.Module):
             raise NotImplementedError("gnpde: ODE regularisation terms are out of scope (SURVEY.md §2 row 12)")
         integrator = self.train_integrator if self.training else self.test_integrator
         t = self.t.type_as(x)
+        # opt-in: explicit_adams / implicit_adams (gnpde.integrator); opt['max_order'], when given, goes
+        # with the key (the reference's blocks pass step_size and max_iters only: torchdiffeq's default 12)
+        adams = {'gnpde_adams': True} if self.opt.get('gnpde_adams') else {}
+        if adams and self.opt.get('max_order') is not None:
+            adams['max_order'] = self.opt['max_order']
+        options = dict(options, **adams)
         if self.opt.get('adjoint', False) and self.training:
             # block_constant.py:34-44: adjoint method / step size / tolerances of their own
             a_opts = {'step_size': self.opt.get('adjoint_step_size', options.get('step_size'))}
             if 'max_iters' in options:
                 a_opts['max_iters'] = options['max_iters']
+            a_opts.update(adams)
             state_dt = integrator(self.odefunc, x, t, method=self.opt['method'], options=options,
                                   adjoint_method=self.opt.get('adjoint_method', self.opt['method']),
                                   adjoint_options=a_opts, atol=self.atol, rtol=self.rtol,

@@ -41,7 +41,7 @@ fp32 rows).
 import torch
 
 from . import ops
-from .integrator import _Combine, _host_grid, _host_times, odeint
+from .integrator import MULTISTEP_METHODS, _Combine, _host_grid, _host_times, odeint
 
 SOLVERS = ('dopri5', 'rk4')
 
@@ -117,6 +117,9 @@ class EarlyStopInt(torch.nn.Module):
     def __call__(self, func, y0, t, method=None, rtol=1e-7, atol=1e-9, adjoint_method="dopri5", adjoint_atol=1e-9,
                  adjoint_rtol=1e-7, options=None):
         method = self.opt['method']
+        if method in MULTISTEP_METHODS:
+            raise NotImplementedError("gnpde.EarlyStopInt: method %r: the early-stop integrator covers dopri5 and rk4 "
+                                      "(as the reference), not the multistep solvers" % method)
         assert method in SOLVERS, "Only dopri5 and rk4 implemented with early stopping"
         if y0.dtype != torch.float32:
             raise NotImplementedError("gnpde.EarlyStopInt: %s state: the score kernel (gnpde_decode_score_f32) reads "

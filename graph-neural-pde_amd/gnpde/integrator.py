@@ -21,15 +21,17 @@ Stage combinations ``y0 + dt * sum_j b_j k_j`` are single fused HIP passes
 ODEFuncs run entirely in HIP).  Parity of integrated values is UNPINNED: the
 reference's tests only check shapes.
 """
+import collections
 import itertools
 import math
 import os
+import warnings
 import weakref
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, adams_coefficients, ops
 from ._cache import _tensor_key
 from .adaptive_backprop import AdaptiveBackprop
 from .adjoint_adaptive import AdaptiveAdjoint
@@ -41,6 +43,9 @@ from .utils import MaxNFEException
 
 FIXED_METHODS = ('euler', 'midpoint', 'rk4')
 ADAPTIVE_METHODS = ('dopri5', 'bosh3', 'fehlberg2', 'adaptive_heun')
+# torchdiffeq's multistep solvers (fixed_adams.AdamsBashforthMoulton), opt-in: taken only with
+# options['gnpde_adams'] true (adjoint_options['gnpde_adams'] for the adjoint solve)
+MULTISTEP_METHODS = ('explicit_adams', 'implicit_adams')
 
 
 class _CombineFn(torch.autograd.Function):
@@ -928,6 +933,233 @@ def _advance(func, method, steps, i, m, p, pool, sg, inplace=False):
     return p
 
 
+# --------------------------------------------------------------------------- multistep (Adams)
+def _combine_chunks(combine, base, ks, coefs, scale, width=_lib.STAGE_MAX_K):
+    """base + scale * sum_j coefs[j] ks[j] for more operands than one combine pass takes
+    (gnpde_rk_combine_f32: 8, the bf16 stage pass: 6): passes of ``width``, each on the last."""
+    acc = base
+    for i in range(0, len(ks), width):
+        acc = combine(acc, list(ks[i:i + width]), list(coefs[i:i + width]), scale)
+    return acc
+
+
+class _AdamsBashforthMoulton(object):
+    """torchdiffeq 0.2.x fixed_adams.AdamsBashforthMoulton restated (explicit_adams: the
+    Adams-Bashforth predictor alone; implicit_adams: with the Adams-Moulton corrector run as a
+    fixed-point iteration), on torchdiffeq's fixed grid with linear interpolation onto the
+    requested times.
+
+    Per step from (t0, y0) to t1 = t0 + dt: f0 = func(t0, y0) joins the front of ``prev_f`` (at
+    most max_order - 1 values, the oldest falls off); order = min(len(prev_f), max_order - 1).
+    order < 3: the step is one rk4 (3/8 rule) step with k1 = f0, nothing else.  Otherwise
+    dy = dt sum_j AB[order][j] prev_f[j]; implicit: with m = AM[order + 1] and delta = dt sum_j
+    m[j + 1] prev_f[j], up to max_iters times  dy <- dt m[0] func(t1, y0 + dy) + delta  until
+    max |dy_old - dy| / (atol + rtol max(|dy_old|, |dy|)) < 1 (a NaN is not converged); a step
+    that never converged warns (once per solve) and drops the oldest entry of prev_f.
+    y1 = y0 + dy.
+
+    Two loops run this: ``_solve_fused`` (no autograd, device fp32 state, a RHS with
+    rhs_stage: f0 and the corrector's f stored by the RHS epilogue, the history in a ring of
+    buffers, the predictor / corrector passes of csrc/adams.hip, the convergence test on the
+    device) and ``_solve_restated`` (anything else: torch tensors through ``combine``, one host
+    decision per corrector iteration as torchdiffeq; autograd flows through it).
+
+    After a solve: ``iterations`` (corrector iterations of every step; 0 for rk4 and explicit
+    steps), ``converged`` (per step), ``ratios`` (the restated loop: every iteration's ratio;
+    the fused loop: the last ratio of each corrector step) and ``path``."""
+
+    def __init__(self, func, y0, rtol, atol, combine, implicit, max_order=None, max_iters=None):
+        max_order = adams_coefficients.MAX_ORDER if max_order is None else int(max_order)
+        if max_order > adams_coefficients.MAX_ORDER:
+            raise ValueError("gnpde.odeint: max_order=%d: the Adams tables end at order %d"
+                             % (max_order, adams_coefficients.MAX_ORDER))
+        if max_order < 4:
+            warnings.warn("gnpde.odeint: max_order=%d < 4: every step of the Adams solver is an rk4 step" % max_order)
+        self.func, self.y0, self.combine, self.implicit = func, y0, combine, implicit
+        self.rtol, self.atol = float(rtol), float(atol)
+        self.hist_len = max(max_order - 1, 0)
+        self.max_iters = 4 if max_iters is None else int(max_iters)
+        self.iterations, self.converged, self.ratios, self.path = [], [], [], None
+        self._warned = False
+
+    def _not_converged(self, t1):
+        if not self._warned:
+            warnings.warn("gnpde.odeint: implicit_adams: the corrector did not converge in %d iterations at t = %g; "
+                          "consider increasing max_iters or reducing step_size" % (self.max_iters, t1))
+            self._warned = True
+
+    def integrate(self, t, step_size):
+        t_h = _host_times(t)
+        grid_h = _host_grid(t_h, t.dtype, step_size)
+        if not (grid_h[0] == t_h[0] and grid_h[-1] == t_h[-1]):
+            raise AssertionError("time grid does not cover t")
+        steps = list(zip(grid_h[:-1], grid_h[1:]))
+        func, y0 = self.func, self.y0
+        if type(func).__module__ == dist_module_name():
+            raise NotImplementedError("gnpde.odeint: explicit_adams / implicit_adams do not cover the sharded RHS "
+                                      "classes of gnpde.dist (the history ring is not sharded); use rk4 or an "
+                                      "adaptive method")
+        if _fusable(func, y0, self.combine) and y0.is_cuda and y0.dtype == torch.float32:
+            self.path = 'fused'
+            return self._solve_fused(t_h, steps)
+        self.path = 'restated'
+        return self._solve_restated(t_h, steps)
+
+    # ---- torch tensors through ``combine``
+    def _solve_restated(self, t_h, steps):
+        func, combine = self.func, self.combine
+        prev_f = collections.deque(maxlen=self.hist_len)
+        solution = [self.y0]
+        j = 1
+        yc = self.y0
+        for ta, tb in steps:
+            dt = tb - ta
+            f0 = func(ta, yc)
+            prev_f.appendleft(f0)
+            order = min(len(prev_f), self.hist_len)
+            its, conv = 0, True
+            if order < 3:  # rk4_alt_step_func with k1 = f0
+                k2 = func(ta + dt / 3.0, combine(yc, [f0], [1.0 / 3.0], dt))
+                k3 = func(ta + dt * 2.0 / 3.0, combine(yc, [f0, k2], [-1.0 / 3.0, 1.0], dt))
+                k4 = func(tb, combine(yc, [f0, k2, k3], [1.0, -1.0, 1.0], dt))
+                y1 = combine(yc, [f0, k2, k3, k4], [0.125, 0.375, 0.375, 0.125], dt)
+            else:
+                hist = list(prev_f)[:order]
+                dy = _combine_chunks(combine, None, hist, adams_coefficients.ADAMS_BASHFORTH[order], dt)
+                if self.implicit:
+                    m = adams_coefficients.ADAMS_MOULTON[order + 1]
+                    delta = _combine_chunks(combine, None, hist, m[1:], dt)
+                    conv = False
+                    for _ in range(self.max_iters):
+                        dy_old = dy
+                        f = func(tb, yc + dy)
+                        dy = combine(delta, [f], [m[0]], dt)
+                        with torch.no_grad():
+                            tol = self.atol + self.rtol * torch.maximum(dy_old.abs(), dy.abs())
+                            ratio = float(((dy_old - dy).abs() / tol).max())
+                        its += 1
+                        self.ratios.append(ratio)
+                        if ratio < 1.0:  # (a NaN compares false)
+                            conv = True
+                            break
+                    if not conv:
+                        self._not_converged(tb)
+                        prev_f.pop()
+                y1 = yc + dy
+            self.iterations.append(its)
+            self.converged.append(conv)
+            while j < len(t_h) and tb >= t_h[j]:
+                solution.append(_linear_interp(ta, tb, yc, y1, t_h[j]))
+                j += 1
+            yc = y1
+        while j < len(t_h):  # a degenerate grid (t0 == t1): the state itself
+            solution.append(yc)
+            j += 1
+        return torch.stack(solution, 0)
+
+    # ---- the HIP passes
+    def _solve_fused(self, t_h, steps):
+        func = self.func
+        y0 = self.y0.contiguous()
+        sol = torch.empty((len(t_h),) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
+        sol[0].copy_(y0)
+        ws = _state_pool(func, y0).ws
+        # the state and its successor (swapped after every step), the rk4 stage inputs, the
+        # increment, the corrector's constant part and its RHS value, and the history ring
+        y, x = ws.get('adams_y', y0), ws.get('adams_x', y0)
+        dy, delta, f = ws.get('adams_dy', y0), ws.get('adams_delta', y0), ws.get('adams_f', y0)
+        free = [ws.get('adams_h%d' % k, y0) for k in range(max(self.hist_len, 1))]
+        status = dict.get(ws, 'adams_status')
+        if status is None or status.device != y0.device:
+            status = ws['adams_status'] = ops.adams_workspace(y0.device)
+        prev_f = collections.deque()
+        y.copy_(y0)
+        chunk = 1  # corrector iterations enqueued before the first status read of a step
+        j = 1
+        for ta, tb in steps:
+            dt = tb - ta
+            # f0 into a ring buffer: the one the oldest entry leaves, or a free one
+            if self.hist_len == 0:
+                slot = free[0]
+            elif len(prev_f) == self.hist_len:
+                slot = prev_f.pop()
+            else:
+                slot = free.pop()
+            order = min(len(prev_f) + 1, self.hist_len)
+            its, conv = 0, True
+            if order < 3:
+                # rk4_alt_step_func with k1 = f0: _fused_step's ping-pong form, the first launch
+                # storing f0 as well
+                a, b, c = ws.get('a', y0), ws.get('b', y0), ws.get('c', y0)
+                func.rhs_stage(ta, y, ops.Stage(f_out=slot, outs=[(a, y, 1.0, dt / 3.0, [])]))
+                if self.hist_len:
+                    prev_f.appendleft(slot)
+                func.rhs_stage(ta + dt / 3.0, a, ops.Stage(outs=[(b, a, -1.0, dt, [(y, 2.0)])]))
+                func.rhs_stage(ta + dt * 2.0 / 3.0, b, ops.Stage(outs=[(c, b, -1.0, dt, [(a, 2.0)])]))
+                func.rhs_stage(tb, c, ops.Stage(outs=[(x, c, 0.375, dt * 0.125, [(b, 0.75), (y, -0.125)])]))
+            else:
+                func.rhs_stage(ta, y, ops.Stage(f_out=slot))
+                prev_f.appendleft(slot)
+                hist = list(prev_f)[:order]
+                cdy = [dt * v for v in adams_coefficients.ADAMS_BASHFORTH[order]]
+                if not self.implicit:
+                    ops.adams_predict(y, hist, cdy, dy, x)
+                else:
+                    m = adams_coefficients.ADAMS_MOULTON[order + 1]
+                    ops.adams_predict(y, hist, cdy, dy, x, cdelta=[dt * v for v in m[1:]], delta=delta)
+                    ops.adams_status_reset(status)
+                    conv, ratio = False, float('nan')
+                    while not conv and its < self.max_iters:
+                        n = max(1, min(chunk if its == 0 else 1, self.max_iters - its))
+                        if n > 1 and not _nfe_headroom(func, n):
+                            n = 1  # near max_nfe: one at a time, the guard raises at the exact call
+                        nfe = getattr(func, 'nfe', None)
+                        for _ in range(n):
+                            func.rhs_stage(tb, x, ops.Stage(f_out=f))
+                            ops.adams_correct(f, delta, y, dy, x, dt * m[0], self.rtol, self.atol, status)
+                        conv, done, ratio = ops.adams_status(status)  # the one host read of the chunk
+                        if nfe is not None:
+                            func.nfe = nfe + (done - its)  # launches behind the converged one were gated off
+                        its = done
+                    if its:
+                        self.ratios.append(ratio)
+                    chunk = max(1, its)
+                    if not conv:
+                        self._not_converged(tb)
+                        free.append(prev_f.pop())
+            self.iterations.append(its)
+            self.converged.append(conv)
+            while j < len(t_h) and tb >= t_h[j]:
+                if t_h[j] == tb:
+                    sol[j].copy_(x)
+                else:
+                    sol[j].copy_(_linear_interp(ta, tb, y, x, t_h[j]))
+                j += 1
+            y, x = x, y
+        while j < len(t_h):  # a degenerate grid (t0 == t1): the state itself
+            sol[j].copy_(y)
+            j += 1
+        return sol
+
+
+def dist_module_name():
+    return __name__.rsplit('.', 1)[0] + '.dist'
+
+
+def odeint_adams(func, y0, t, method, rtol, atol, options, combine):
+    """explicit_adams / implicit_adams (options: step_size, max_order <= 12, max_iters)."""
+    if options.get('gnpde_accept_hook') is not None or options.get('gnpde_max_attempts') is not None:
+        raise NotImplementedError("gnpde.odeint: the early-stop hooks cover rk4 and the adaptive methods, not %s"
+                                  % method)
+    solver = _AdamsBashforthMoulton(func, y0, rtol, atol, combine, method == 'implicit_adams',
+                                    max_order=options.get('max_order'), max_iters=options.get('max_iters'))
+    out = solver.integrate(t, options.get('step_size'))
+    odeint.last_path = 'adams_' + solver.path
+    odeint.last_n_steps = len(solver.iterations)
+    odeint.last_adams = {'iterations': solver.iterations, 'converged': solver.converged, 'ratios': solver.ratios}
+    return out
+
+
 class _RKAdaptive(object):
     """torchdiffeq RKAdaptiveStepsizeODESolver (0.2.x rk_common.py) restated for an
     explicit embedded tableau (dopri5, bosh3, fehlberg2, adaptive_heun)."""
@@ -1804,12 +2036,21 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, combine
         odeint.last_capped = solver.capped
         odeint.last_dense_fold = bool(getattr(solver, 'fold', False))
         return out
+    if method in MULTISTEP_METHODS:
+        if options.get('gnpde_adams'):
+            return odeint_adams(func, y0, t, method, rtol, atol, options, combine)
+        raise NotImplementedError("gnpde.odeint: method %r is opt-in: set options['gnpde_adams'] = True "
+                                  "(adjoint_options['gnpde_adams'] for the adjoint solve; ODEblock sets both from "
+                                  "opt['gnpde_adams'])" % method)
     raise NotImplementedError("gnpde.odeint: method %r not supported (supported: %s)" %
                               (method, ', '.join(FIXED_METHODS + ADAPTIVE_METHODS)))
 
 
 odeint.last_n_steps = 0
-odeint.last_path = None  # the last adaptive solve's loop: 'fused_krylov', 'fused_stage' or 'restated'
+# the last adaptive or multistep solve's loop: 'fused_krylov', 'fused_stage', 'restated', 'adams_fused' or
+# 'adams_restated'
+odeint.last_path = None
+odeint.last_adams = None  # the last multistep solve: per-step corrector 'iterations', 'converged', and 'ratios'
 odeint.last_capped = False  # whether it stopped at options['gnpde_max_attempts'] before the output time
 odeint.last_dense_fold = False  # whether its dense output was folded into the steps (DENSE_FOLD)
 
@@ -1906,7 +2147,7 @@ class _OdeintAdjoint(torch.autograd.Function):
     def forward(ctx, y0, t, cfg, *params):
         func, rtol, atol, method, options = cfg[:5]
         with torch.no_grad():
-            ans = odeint(func, y0, t, rtol=rtol, atol=atol, method=method, options=options)
+            ans = odeint(func, y0, t, rtol=rtol, atol=atol, method=method, options=options, combine=cfg[9])
         ctx.cfg = cfg
         ctx.params = params  # the leaf parameters themselves: the VJPs are taken with respect to them
         ctx.save_for_backward(t, ans)
@@ -1914,7 +2155,7 @@ class _OdeintAdjoint(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_y):
-        func, _rtol, _atol, _method, _options, a_rtol, a_atol, a_method, a_options = ctx.cfg
+        func, _rtol, _atol, _method, _options, a_rtol, a_atol, a_method, a_options, combine = ctx.cfg
         t, ans = ctx.saved_tensors
         params = ctx.params
         if _adaptive_adjoint_ok(func, ans, a_method, params, a_options):
@@ -1930,8 +2171,10 @@ class _OdeintAdjoint(torch.autograd.Function):
         ny = ans[0].numel()
         sizes = [ny, ny] + [p.numel() for p in params]
 
+        pdt = torch.float64 if ans.dtype == torch.float64 else torch.float32  # (fp64: the host tests)
+
         def pack(y, ay, ap):
-            return torch.cat([y.reshape(-1).float(), ay.reshape(-1).float()] + [a.reshape(-1).float() for a in ap])
+            return torch.cat([y.reshape(-1).to(pdt), ay.reshape(-1).to(pdt)] + [a.reshape(-1).to(pdt) for a in ap])
 
         def aug_autograd(s, z):
             y = z[:ny].view(y_shape)
@@ -1963,7 +2206,8 @@ class _OdeintAdjoint(torch.autograd.Function):
                 for i in range(len(t) - 1, 0, -1):
                     z0 = pack(ans[i], ay, ap)
                     s = torch.stack([-t[i], -t[i - 1]])
-                    z1 = odeint(aug, z0, s, rtol=a_rtol, atol=a_atol, method=a_method, options=opts)[1]
+                    z1 = odeint(aug, z0, s, rtol=a_rtol, atol=a_atol, method=a_method, options=opts,
+                                combine=combine)[1]
                     ay = z1[ny:2 * ny].view(y_shape).to(grad_y.dtype) + grad_y[i - 1]
                     o = 2 * ny
                     ap = []
@@ -2102,12 +2346,13 @@ class _LaplacianAdjointFn(torch.autograd.Function):
 
 
 def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, adjoint_rtol=None,
-                   adjoint_atol=None, adjoint_method=None, adjoint_options=None, adjoint_params=None):
+                   adjoint_atol=None, adjoint_method=None, adjoint_options=None, adjoint_params=None, combine=None):
     """torchdiffeq.odeint_adjoint(func, y0, t, ...) with its defaults: the adjoint
     tolerances / method default to the forward ones, adjoint_options to the
     forward options (without 'norm') when the methods match, adjoint_params to
     func's parameters that require grad.  Gradients reach y0 and adjoint_params
-    (as in torchdiffeq, not other tensors the RHS closes over)."""
+    (as in torchdiffeq, not other tensors the RHS closes over).  ``combine``: odeint's
+    (the host tests inject _torch_combine for CPU tensors; None: the HIP stage combinations)."""
     method = method or 'dopri5'
     if adjoint_params is None:
         adjoint_params = tuple(p for p in func.parameters() if p.requires_grad)
@@ -2120,10 +2365,11 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
             else {}
     if not isinstance(t, torch.Tensor):
         t = torch.as_tensor(t)
-    cfg = (func, rtol, atol, method, options, adjoint_rtol, adjoint_atol, adjoint_method, adjoint_options)
+    cfg = (func, rtol, atol, method, options, adjoint_rtol, adjoint_atol, adjoint_method, adjoint_options, combine)
     if _fused_adjoint_ok(func, y0, adjoint_method, adjoint_params):
         return _LaplacianAdjointFn.apply(y0, t, cfg, *adjoint_params)
     return _OdeintAdjoint.apply(y0, t, cfg, *adjoint_params)
 
 
-__all__ = ['odeint', 'odeint_adjoint', 'fixed_grid', 'FIXED_METHODS', 'ADAPTIVE_METHODS', 'math']
+__all__ = ['odeint', 'odeint_adjoint', 'fixed_grid', 'FIXED_METHODS', 'ADAPTIVE_METHODS', 'MULTISTEP_METHODS',
+           'math']

@@ -2063,6 +2063,75 @@ def rk_combine(y0, ks, coefs, scale, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- multistep (Adams) passes
+def _adams_operand(t, name, like):
+    _require_gpu(t, name, torch.float32)
+    if not t.is_contiguous() or t.numel() != like.numel():
+        raise ValueError("adams: %s must be contiguous and sized like y0" % name)
+
+
+def adams_predict(y0, hist, cdy, dy, x, cdelta=None, delta=None):
+    """gnpde_adams_predict_f32: dy = sum_j cdy[j] hist[j], x = y0 + dy and (with ``cdelta`` /
+    ``delta``) delta = sum_j cdelta[j] hist[j], from one read of y0 and of every history array
+    (newest first, at most _lib.ADAMS_MAX_HISTORY); fp64 sums, one rounding per stored value.
+    The coefficients carry the step size."""
+    _require_gpu(y0, "y0", torch.float32)
+    if not y0.is_contiguous():
+        raise ValueError("adams: y0 must be contiguous")
+    nh = len(hist)
+    if not 1 <= nh <= _lib.ADAMS_MAX_HISTORY or len(cdy) != nh or (cdelta is not None and len(cdelta) != nh):
+        raise ValueError("adams_predict: 1 to %d history arrays, one coefficient each" % _lib.ADAMS_MAX_HISTORY)
+    if (cdelta is None) != (delta is None):
+        raise ValueError("adams_predict: cdelta and delta go together")
+    for t, nm in ((dy, "dy"), (x, "x")) + (((delta, "delta"),) if delta is not None else ()):
+        _adams_operand(t, nm, y0)
+    hp = (ctypes.c_void_p * nh)()
+    c1 = (ctypes.c_double * nh)()
+    c2 = (ctypes.c_double * nh)() if cdelta is not None else None
+    for j, h in enumerate(hist):
+        _adams_operand(h, "hist[%d]" % j, y0)
+        hp[j] = h.data_ptr()
+        c1[j] = float(cdy[j])
+        if c2 is not None:
+            c2[j] = float(cdelta[j])
+    _lib.call("gnpde_adams_predict_f32", y0.numel(), _ptr(y0), nh, hp, c1, c2, _ptr(dy), _ptr(x), _ptr(delta),
+              _stream(y0.device))
+    return dy, x, delta
+
+
+def adams_workspace(device):
+    """The corrector's workspace, zeroed: int32 words, the first four the status record
+    {converged, iterations, ratio (fp32 bits), reserved} (gnpde_adams_status_t)."""
+    return torch.zeros(_lib.call_rc("gnpde_adams_workspace_bytes") // 4, dtype=torch.int32, device=device)
+
+
+def adams_status_reset(ws):
+    """Zero the status record and the arrival counter, in stream order (once per step)."""
+    _require_gpu(ws, "ws", torch.int32)
+    _lib.call("gnpde_adams_status_reset", _ptr(ws), _stream(ws.device))
+
+
+def adams_correct(f, delta, y0, dy, x, cf, rtol, atol, ws):
+    """gnpde_adams_correct_f32: one gated corrector iteration — unless ws's status says converged,
+    dy <- cf f + delta, x <- y0 + dy, status <- {ratio < 1, iterations + 1, ratio} with ratio =
+    max |dy_old - dy| / (atol + rtol max(|dy_old|, |dy|)) (a NaN propagates)."""
+    _require_gpu(y0, "y0", torch.float32)
+    _require_gpu(ws, "ws", torch.int32)
+    if not y0.is_contiguous():
+        raise ValueError("adams: y0 must be contiguous")
+    for t, nm in ((f, "f"), (delta, "delta"), (dy, "dy"), (x, "x")):
+        _adams_operand(t, nm, y0)
+    _lib.call("gnpde_adams_correct_f32", y0.numel(), _ptr(f), _ptr(delta), _ptr(y0), float(cf), float(rtol),
+              float(atol), _ptr(dy), _ptr(x), _ptr(ws), ws.numel() * 4, _stream(y0.device))
+
+
+def adams_status(ws):
+    """(converged, iterations, ratio) of the status record: one host read (it waits for the
+    stream)."""
+    rec = ws[:4].cpu()
+    return bool(rec[0].item()), int(rec[1].item()), float(rec[2:3].view(torch.float32).item())
+
+
 # --------------------------------------------------------------------------- early-stop scoring
 def decode_score_torch(y, W, b, split, label, counts_out, ld=None, rows=None, pred_out=None):
     """gnpde_decode_score_f32 restated in torch ops (any device, no host read): the path

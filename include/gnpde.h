@@ -953,6 +953,48 @@ int gnpde_knn_f32(const float* x, int64_t B, int64_t N, int64_t C, int64_t ld, i
 int gnpde_cross_attention_f32(const float* q, int64_t ldq, const float* k, const float* v, int64_t B, int64_t N,
                               int64_t M, int64_t C, float scale, float* out, int64_t ldo, float* lse, void* stream);
 
+/* The Adams-Bashforth-Moulton multistep solvers (gnpde.integrator: explicit_adams /
+ * implicit_adams; entry points added under ABI 8).  fp32 arrays of n elements, no
+ * aliasing except where stated; everything is enqueued on the stream.
+ *
+ * Predictor: one read of y0 and of each of the nh (1 <= nh <= GNPDE_ADAMS_MAX_HISTORY)
+ * history arrays hist[j] (newest first),
+ *   dy[i]    = fl32(sum_j cdy[j] hist[j][i])
+ *   x[i]     = fl32(y0[i] + sum_j cdy[j] hist[j][i])
+ *   delta[i] = fl32(sum_j cdelta[j] hist[j][i])        (delta and cdelta both NULL: skipped)
+ * each sum carried in fp64 per element (j ascending, fused multiply-adds) and rounded to
+ * fp32 once at its store; the coefficients arrive multiplied by dt.                      */
+#define GNPDE_ADAMS_MAX_HISTORY 11
+int gnpde_adams_predict_f32(int64_t n, const float* y0, int nh, const float* const* hist, const double* cdy,
+                            const double* cdelta, float* dy, float* x, float* delta, void* stream);
+
+/* The corrector's device status record (16 bytes) followed by the reduction's arrival
+ * counter; the workspace of gnpde_adams_correct_f32 starts with one.                     */
+typedef struct {
+  int32_t converged;  /* 1 once an iteration's ratio was < 1                                */
+  int32_t iterations; /* corrector iterations applied (launches that were not gated off)    */
+  float ratio;        /* the last applied iteration's convergence ratio (NaN propagates)    */
+  int32_t reserved;
+  uint32_t arrivals;  /* workgroups that finished the running launch (0 between launches)   */
+  uint32_t pad[3];
+} gnpde_adams_status_t;
+size_t gnpde_adams_workspace_bytes(void);
+/* Zero the status record and the arrival counter (a memset node; once per step).         */
+int gnpde_adams_status_reset(void* workspace, void* stream);
+/* One corrector iteration, gated: a launch that finds status.converged set returns without
+ * touching dy, x or the status.  Otherwise, with d = dy[i] before the launch,
+ *   dy[i] = fl32(cf f[i] + delta[i])         (fp64 multiply-add, one rounding)
+ *   x[i]  = fl32(y0[i] + cf f[i] + delta[i]) (the same fp64 sum, one rounding)
+ *   ratio = max_i |d - dy[i]| / (atol + rtol max(|d|, |dy[i]|))   (numerators and denominators
+ *           in fp64 per element, compared by cross-multiplication; a NaN quotient anywhere
+ *           (a NaN operand, 0 / 0, inf / inf) makes the ratio NaN)
+ * and status becomes {converged = ratio < 1, iterations + 1, ratio}.  The ratio is reduced
+ * per workgroup and finished by the workgroup that arrives last: a fixed reduction of a
+ * maximum, the same bits on every run.  workspace: gnpde_adams_workspace_bytes() bytes,
+ * 16-byte aligned, reset by gnpde_adams_status_reset before the first iteration of a step. */
+int gnpde_adams_correct_f32(int64_t n, const float* f, const float* delta, const float* y0, double cf, double rtol,
+                            double atol, float* dy, float* x, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
