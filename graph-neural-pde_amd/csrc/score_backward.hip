@@ -25,6 +25,14 @@
 // One wavefront per row (64-thread workgroups); lane j holds elements j, j+64, ...
 // of the att-wide rows; per-head sums meet in LDS (any dk).  Fixed summation
 // order everywhere: deterministic.
+//
+// gnpde_score_grad_split_f32 is the exp_kernel path for a head whose dk elements are
+// two parts, [0, dk_split) and [dk_split, dk) (the beltrami product kernel: the feature
+// and the positional projections of a head, each already divided by its lengthscale,
+// side by side).  The score and dL/dq, dL/dk are those of exp_kernel
+// over the whole head; the squared distance is summed per part (in LDS, at granularity
+// dk_split, any value) so that each part's lengthscale gets its own per-edge term:
+//   gp[e, h] = g_s 2 s / p0,  gp[e, H+h] = g_s s |d_a|^2 / p1^2,  gp[e, 2H+h] = g_s s |d_b|^2 / p1^2.
 #include "common.hpp"
 
 namespace gnpde {
@@ -50,7 +58,8 @@ struct ScoreGradArgs {
   const float* gs;  // [E, H] COO
   float* out;       // [R, ldo]
   int64_t ldo;
-  float* gp;  // [E, 2H] COO or NULL
+  float* gp;  // [E, 2H] COO or NULL ([E, 3H]: the split kernel)
+  int dk_split;  // the split kernel: width of a head's first part
 };
 
 // per-head sum of v over the dk elements of each head, via the wave's LDS row
@@ -73,6 +82,86 @@ __device__ __forceinline__ void head_sums(float* lds, const float (&v)[kPass], i
     out[t] = s;
   }
   __syncthreads();
+}
+
+// per-part sums of v over each head: oa over its first dks elements, ob over the other dk - dks
+__device__ __forceinline__ void part_sums(float* lds, const float (&v)[kPass], int att, int dk, int dks,
+                                          float (&oa)[kPass], float (&ob)[kPass]) {
+  const int lane = threadIdx.x;
+#pragma unroll
+  for (int t = 0; t < kPass; ++t) {
+    const int j = lane + t * kWave;
+    if (j < att) lds[j] = v[t];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < kPass; ++t) {
+    const int j = lane + t * kWave;
+    float sa = 0.f, sb = 0.f;
+    if (j < att) {
+      const int h0 = (j / dk) * dk;
+      for (int d = 0; d < dks; ++d) sa += lds[h0 + d];
+      for (int d = dks; d < dk; ++d) sb += lds[h0 + d];
+    }
+    oa[t] = sa;
+    ob[t] = sb;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void score_grad_split_kernel(ScoreGradArgs a) {
+  __shared__ float lds[kMaxAtt];
+  const int lane = threadIdx.x;
+  const int npass = (a.att + kWave - 1) / kWave;
+  const float* own_base = a.side == 0 ? a.q : a.k;
+  const float* oth_base = a.side == 0 ? a.k : a.q;
+  const float rl2 = 1.0f / (a.p1 * a.p1);
+  for (int64_t r = blockIdx.x; r < a.R; r += gridDim.x) {
+    float own[kPass], acc[kPass], A[kPass];
+#pragma unroll
+    for (int t = 0; t < kPass; ++t) {
+      const int j = lane + t * kWave;
+      own[t] = (t < npass && j < a.att) ? own_base[r * a.ldqk + j] : 0.f;
+      acc[t] = 0.f;
+      A[t] = 0.f;
+    }
+    const int b = a.rowptr[r], e_end = a.rowptr[r + 1];
+    for (int p = b; p < e_end; ++p) {
+      const int oth_node = a.col[p];
+      const int64_t e = a.perm[p];
+      float oth[kPass], prod[kPass], Sa[kPass], Sb[kPass];
+#pragma unroll
+      for (int t = 0; t < kPass; ++t) {
+        const int j = lane + t * kWave;
+        oth[t] = (t < npass && j < a.att) ? oth_base[(int64_t)oth_node * a.ldqk + j] : 0.f;
+        const float d = own[t] - oth[t];
+        prod[t] = d * d;
+      }
+      part_sums(lds, prod, a.att, a.dk, a.dk_split, Sa, Sb);
+#pragma unroll
+      for (int t = 0; t < kPass; ++t) {
+        const int j = lane + t * kWave;
+        if (t >= npass || j >= a.att) continue;
+        const int h = j / a.dk;
+        const float g = a.gs[e * a.H + h];
+        const float s = a.p0 * a.p0 * expf(-0.5f * rl2 * (Sa[t] + Sb[t]));
+        const float a_oth = s * rl2;
+        if (a.gp != nullptr && j % a.dk == 0) {  // one lane per head: the parameter terms
+          float* gp = a.gp + e * 3 * a.H;
+          gp[h] = g * 2.0f * s / a.p0;
+          gp[a.H + h] = g * s * Sa[t] * rl2;
+          gp[2 * a.H + h] = g * s * Sb[t] * rl2;
+        }
+        A[t] = fmaf(g, -a_oth, A[t]);
+        acc[t] = fmaf(g * a_oth, oth[t], acc[t]);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < kPass; ++t) {
+      const int j = lane + t * kWave;
+      if (t < npass && j < a.att) a.out[r * a.ldo + j] = fmaf(own[t], A[t], acc[t]);
+    }
+  }
 }
 
 __global__ __launch_bounds__(64) void score_grad_kernel(ScoreGradArgs a) {
@@ -192,9 +281,33 @@ int gnpde_score_grad_f32(const int32_t* rowptr, const int32_t* col, const int32_
                 "score_grad: NULL pointer");
   GNPDE_REQUIRE(R < (int64_t)INT32_MAX && nnz < (int64_t)INT32_MAX, GNPDE_EUNSUPPORTED, "score_grad: too large");
   ScoreGradArgs a{rowptr, col, perm, R, side, mode, (int)heads, (int)dk, (int)(heads * dk), q, k, ldqk,
-                  score_p0, score_p1, gs, out, ldo, gp};
+                  score_p0, score_p1, gs, out, ldo, gp, 0};
   const int64_t grid = R < 65536 ? R : 65536;
   score_grad_kernel<<<(unsigned)grid, kWave, 0, as_stream(stream)>>>(a);
+  GNPDE_LAUNCH_CHECK();
+  return GNPDE_OK;
+}
+
+int gnpde_score_grad_split_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t R, int64_t nnz,
+                               int side, int64_t heads, int64_t dk, int64_t dk_split, const float* q, const float* k,
+                               int64_t ldqk, float score_p0, float score_p1, const float* gs, float* out, int64_t ldo,
+                               float* gp, void* stream) {
+  GNPDE_REQUIRE(side == 0 || side == 1, GNPDE_EINVAL, "score_grad_split: side must be 0 or 1");
+  GNPDE_REQUIRE(heads >= 1 && dk >= 1 && heads * dk <= kMaxAtt, GNPDE_EUNSUPPORTED,
+                "score_grad_split: attention_dim %lld > %d", (long long)(heads * dk), kMaxAtt);
+  GNPDE_REQUIRE(dk_split >= 0 && dk_split <= dk, GNPDE_EINVAL, "score_grad_split: dk_split %lld outside [0, dk = %lld]",
+                (long long)dk_split, (long long)dk);
+  GNPDE_REQUIRE(score_p0 != 0.f && score_p1 != 0.f, GNPDE_EINVAL, "score_grad_split: zero score parameter");
+  GNPDE_REQUIRE(R >= 1 && nnz >= 0 && ldqk >= heads * dk && ldo >= heads * dk, GNPDE_EINVAL,
+                "score_grad_split: bad sizes");
+  GNPDE_REQUIRE(rowptr && out && (nnz == 0 || (col && perm && q && k && gs)), GNPDE_EINVAL,
+                "score_grad_split: NULL pointer");
+  GNPDE_REQUIRE(R < (int64_t)INT32_MAX && nnz < (int64_t)INT32_MAX, GNPDE_EUNSUPPORTED,
+                "score_grad_split: too large");
+  ScoreGradArgs a{rowptr, col, perm, R, side, GNPDE_SCORE_EXP_KERNEL, (int)heads, (int)dk, (int)(heads * dk), q, k,
+                  ldqk, score_p0, score_p1, gs, out, ldo, gp, (int)dk_split};
+  const int64_t grid = R < 65536 ? R : 65536;
+  score_grad_split_kernel<<<(unsigned)grid, kWave, 0, as_stream(stream)>>>(a);
   GNPDE_LAUNCH_CHECK();
   return GNPDE_OK;
 }

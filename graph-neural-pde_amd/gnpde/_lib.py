@@ -147,6 +147,8 @@ SIGNATURES = {
     "gnpde_norm_weights_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp]),
     "gnpde_score_grad_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _f32, _f32, _vp,
                                     _vp, _i64, _vp, _vp]),
+    "gnpde_score_grad_split_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _f32, _f32,
+                                          _vp, _vp, _i64, _vp, _vp]),
     "gnpde_gat_scores_workspace_bytes": (_size, [_i64, _i64]),
     "gnpde_gat_scores_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _size, _vp]),
     "gnpde_attn_gat_rhs_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _int, _i64, _f32, _i64, _vp, _i64, _vp,

@@ -517,6 +517,16 @@ def _refuse_square_plus(square_plus, who):
                                   "opt['gnpde_square_plus'])" % who)
 
 
+def _refuse_beltrami_kernel(beltrami_kernel, who):
+    """The sharded attention classes project with one Q and one K over every column of the
+    state; the beltrami product kernel (split Qx / Kx / Qp / Kp projections folded into one
+    operand) is a single-GPU path."""
+    if beltrami_kernel:
+        raise NotImplementedError("%s: the beltrami exp_kernel attention (gnpde_beltrami_kernel) is not sharded; "
+                                  "run it on one GPU (gnpde.ODEFuncTransformerAtt with "
+                                  "opt['gnpde_beltrami_kernel'])" % who)
+
+
 class _HipAttentionLocal(object):
     """A rank's arithmetic of the sharded transformer RHS on the HIP path (tests
     inject a CPU object with the same methods to run the collectives under gloo)."""
@@ -687,9 +697,10 @@ class ColumnShardedTransformer(object):
     def __init__(self, edge_index, num_nodes, C, Wq, bq, Wk, bk, heads, norm_idx, alpha, score_mode='reference',
                  beta=None, x0_local=None, add_source=False, alpha_sigmoid=True, group=None, local=None,
                  chunk=None, comm=None, partition_stats=True, edge_weights=None, square_plus=False,
-                 mix_features=False):
+                 mix_features=False, beltrami_kernel=False):
         _refuse_square_plus(square_plus, "ColumnShardedTransformer")
         _refuse_mix_features(mix_features, "ColumnShardedTransformer")
+        _refuse_beltrami_kernel(beltrami_kernel, "ColumnShardedTransformer")
         self.group = group
         self.comm = comm if comm is not None else _Comm(group)
         self.rank = dist.get_rank(group)
@@ -959,9 +970,10 @@ class RowShardedTransformer(object):
     def __init__(self, edge_index, num_nodes, C, Wq, bq, Wk, bk, heads, norm_idx, alpha, score_mode='reference',
                  beta=None, x0_local=None, add_source=False, alpha_sigmoid=True, group=None,
                  chunk=None, row_weight=ROW_WEIGHT, comm=None, local=None, partition_stats=True, square_plus=False,
-                 mix_features=False):
+                 mix_features=False, beltrami_kernel=False):
         _refuse_square_plus(square_plus, "RowShardedTransformer")
         _refuse_mix_features(mix_features, "RowShardedTransformer")
+        _refuse_beltrami_kernel(beltrami_kernel, "RowShardedTransformer")
         if edge_index.shape[0] != 1:
             raise NotImplementedError("RowShardedTransformer: one graph (B = 1); shard batches with shard_batch")
         if int(norm_idx) not in (0, 1) or score_mode not in ('reference', 'per_edge'):

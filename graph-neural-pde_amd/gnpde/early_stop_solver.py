@@ -90,6 +90,10 @@ class EarlyStopInt(torch.nn.Module):
 
     def __init__(self, t, opt, device=None, scorer=None):
         super(EarlyStopInt, self).__init__()
+        if opt.get('beltrami', False) and opt.get('attention_type', 'scaled_dot') == 'exp_kernel' and \
+                opt.get('gnpde_beltrami_kernel', False):
+            raise NotImplementedError("gnpde.EarlyStopInt: the beltrami exp_kernel attention "
+                                      "(gnpde_beltrami_kernel) is not covered by the early-stop integrator")
         self.device = device
         self.solver = None
         self.data = None

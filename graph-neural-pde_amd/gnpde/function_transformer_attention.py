@@ -52,8 +52,26 @@ cores (gnpde_linear_f32), the per-head aggregation (gnpde_head_aggregate_f32,
 csrc/head_aggregate.hip: K1's plan items, per-head weights, the heads reduced across
 lanes) and Wout with its bias and the RHS / stage epilogue fused
 (gnpde_linear_rhs_bias_f32).  fp32 states, one GPU, the user's node numbering.
-DESIGN.md §6.16.  Settings the fork cannot execute (``mix_features`` without
-``gnpde_mix_features``, ``square_plus`` :264 without ``gnpde_square_plus``, ``multi_modal`` :171/222, beltrami+exp_kernel :164-167)
+DESIGN.md §6.16.
+
+The beltrami product kernel (``beltrami`` with ``attention_type='exp_kernel'``, :90-123 and
+:164-216) runs when the option dict also sets ``opt['gnpde_beltrami_kernel'] = True``: the
+reference slices the node axis where it means the feature axis (:166-167), and the key selects
+what the branch means.  With C = hidden_dim, F = feat_hidden_dim, P = pos_enc_hidden_dim and the
+state columns [features F | positions P | labels C-F-P]:
+  p = x[..., F:F+P],  xf = cat(x[..., :F], x[..., F+P:])
+  s[b,e,h] = ovx^2 exp(-|Qx(xf)_src,h - Kx(xf)_dst,h|^2 / (2 lsx^2)) ovp^2 exp(-|Qp(p)_src,h - Kp(p)_dst,h|^2 / (2 lsp^2))
+Since the two exponents add to |q' - k'|^2 / 2 with q'_h = [qx_h / lsx | qp_h / lsp], the score is
+exp_kernel with heads h, dk' = 2 dk, p0 = ovx ovp, p1 = 1 over ONE folded projection operand
+W' [4 att, C] (``fold_beltrami``, cached per parameter version as ``wcat()`` is): every forward
+pass above runs unchanged.  Backward (``_BeltramiAttention``): gnpde_score_grad_split_f32 gives
+dL/dq', dL/dk' and the per-edge terms of the four scalars' gradients (summed in fp64), the
+projection backward runs over W', and ``unfold_beltrami`` takes its result back to Qx / Kx / Qp /
+Kp.  Vx, Vp and Wout are dead (v = None, :216).  DESIGN.md §6.22.
+
+Settings the fork cannot execute (``mix_features`` without
+``gnpde_mix_features``, ``square_plus`` :264 without ``gnpde_square_plus``, ``multi_modal`` :171/222,
+beltrami+exp_kernel :164-167 without ``gnpde_beltrami_kernel``)
 raise NotImplementedError.  ``reweight_attention`` is a no-op in the fork (the
 layer's ``edge_weights`` is captured as None at construction, :15 / :261) and
 is a no-op here.
@@ -100,8 +118,80 @@ def _check_supported(opt):
                                   "transformer function (opt['gnpde_multi_modal'] serves function='laplacian' "
                                   "under block='constant' only)")
     if opt.get('beltrami', False) and opt.get('attention_type', 'scaled_dot') == 'exp_kernel':
-        raise NotImplementedError("gnpde: the beltrami exp_kernel branch slices nodes instead of features in the "
-                                  "reference (:166-167) and is not implemented")
+        if not opt.get('gnpde_beltrami_kernel', False):
+            raise NotImplementedError("gnpde: the beltrami exp_kernel branch slices nodes instead of features in the "
+                                      "reference (:166-167); set opt['gnpde_beltrami_kernel'] = True to run the "
+                                      "intended slices, p = x[..., F:F+P] and x[..., :F] | x[..., F+P:]")
+        if opt.get('mix_features', False):
+            raise NotImplementedError("gnpde: mix_features with the beltrami exp_kernel branch "
+                                      "(gnpde_beltrami_kernel): the reference's branch returns v = None (:216), "
+                                      "so there are no values to mix")
+
+
+def beltrami_kernel(opt):
+    """Whether ``opt`` selects the beltrami product kernel (:90-123, :164-216): ``beltrami``,
+    ``attention_type='exp_kernel'`` and the opt-in key ``gnpde_beltrami_kernel`` (the key
+    alone changes nothing)."""
+    return bool(opt.get('beltrami', False) and opt.get('attention_type', 'scaled_dot') == 'exp_kernel' and
+                opt.get('gnpde_beltrami_kernel', False))
+
+
+def beltrami_widths(opt, in_features):
+    """(C, F, P) of the state layout [features F | positions P | labels C - F - P]
+    (GNN.py:23-40, base_classes.py:149-162), checked."""
+    C = int(opt['hidden_dim'])
+    if int(in_features) != C:
+        raise ValueError("gnpde: gnpde_beltrami_kernel: in_features %d != opt['hidden_dim'] %d (augment): the "
+                         "reference sizes Qx from opt['hidden_dim'], not from in_features" % (in_features, C))
+    if 'feat_hidden_dim' not in opt or 'pos_enc_hidden_dim' not in opt:
+        raise ValueError("gnpde: gnpde_beltrami_kernel needs opt['feat_hidden_dim'] and opt['pos_enc_hidden_dim']")
+    F, P = int(opt['feat_hidden_dim']), int(opt['pos_enc_hidden_dim'])
+    if F < 1 or P < 1 or F + P > C:
+        raise ValueError("gnpde: gnpde_beltrami_kernel: feat_hidden_dim %d and pos_enc_hidden_dim %d must be >= 1 "
+                         "and sum to at most hidden_dim %d" % (F, P, C))
+    return C, F, P
+
+
+def fold_beltrami(Wqx, bqx, Wkx, bkx, Wqp, bqp, Wkp, bkp, lsx, lsp, heads, F, P, C):
+    """The folded projection (W' [4 att, C], b' [4 att]) of the product kernel: since
+      |qx - kx|^2 / (2 lsx^2) + |qp - kp|^2 / (2 lsp^2) = |q' - k'|^2 / 2,  q'_h = [qx_h / lsx | qp_h / lsp],
+    the score is exp_kernel at heads = h, dk' = 2 dk, p0 = ovx ovp, p1 = 1.  Rows: q' then k'
+    (2 att each); in each, head h owns rows h 2dk ..: dk rows of Qx (Kx) / lsx in the feature and
+    label columns [0,F) + [F+P,C), then dk rows of Qp (Kp) / lsp in the columns [F,F+P); zero
+    elsewhere.  torch ops on the parameters' device, the lengthscales never read on the host."""
+    att = Wqx.shape[0]
+    dk = att // heads
+    dev = Wqx.device
+    xcols = torch.cat([torch.arange(0, F, device=dev), torch.arange(F + P, C, device=dev)])
+    pcols = torch.arange(F, F + P, device=dev)
+    W = torch.zeros(2, heads, 2, dk, C, dtype=Wqx.dtype, device=dev)
+    b = torch.zeros(2, heads, 2, dk, dtype=Wqx.dtype, device=dev)
+    for side, (Wx, bx, Wp, bp) in enumerate(((Wqx, bqx, Wqp, bqp), (Wkx, bkx, Wkp, bkp))):
+        W[side, :, 0].index_copy_(2, xcols, (Wx / lsx).view(heads, dk, C - P))
+        W[side, :, 1].index_copy_(2, pcols, (Wp / lsp).view(heads, dk, P))
+        b[side, :, 0] = (bx / lsx).view(heads, dk)
+        b[side, :, 1] = (bp / lsp).view(heads, dk)
+    return W.view(4 * att, C), b.view(4 * att)
+
+
+def unfold_beltrami(gW, gb, lsx, lsp, heads, F, P, C):
+    """fold_beltrami's transpose: the gradients of (W', b') taken back to (Wqx, bqx, Wkx, bkx,
+    Wqp, bqp, Wkp, bkp) at fixed lengthscales (their own gradients come per edge,
+    ops.score_grad_split)."""
+    att = gW.shape[0] // 4
+    dk = att // heads
+    dev = gW.device
+    xcols = torch.cat([torch.arange(0, F, device=dev), torch.arange(F + P, C, device=dev)])
+    pcols = torch.arange(F, F + P, device=dev)
+    gW = gW.view(2, heads, 2, dk, C)
+    gb = gb.view(2, heads, 2, dk)
+    out = []
+    for part, (cols, ls) in enumerate(((xcols, lsx), (pcols, lsp))):
+        for side in (0, 1):
+            out.append((gW[side, :, part].index_select(2, cols).reshape(att, cols.numel()) / ls,
+                        gb[side, :, part].reshape(att) / ls))
+    (gWqx, gbqx), (gWkx, gbkx), (gWqp, gbqp), (gWkp, gbkp) = out
+    return gWqx, gbqx, gWkx, gbkx, gWqp, gbqp, gWkp, gbkp
 
 
 def _needs_grad(*ts):
@@ -150,6 +240,49 @@ class _EdgeAttention(torch.autograd.Function):
                 (so, do), (sl, dl) = ctx.p_shapes
                 g_ov, g_ls = gp[0].reshape(so).to(do), gp[1].reshape(sl).to(dl)
         return grads + (g_ov, g_ls, None, None, None)
+
+
+class _BeltramiAttention(torch.autograd.Function):
+    """attention [B,E,h] (COO) of the beltrami product kernel as a function of x, the eight
+    Qx / Kx / Qp / Kp tensors and the four scalars.  Forward: the exp_kernel passes over the
+    folded projection (fold_beltrami).  Backward: the normaliser's backward, then
+    gnpde_score_grad_split_f32 per side (dL/dq', dL/dk' and, summed per edge in fp64,
+      S0 = sum g_s 2 s / (ovx ovp),  S1 = sum g_s s |q'x - k'x|^2,  S2 = sum g_s s |q'p - k'p|^2,
+    so g_ovx = ovp S0, g_ovp = ovx S0, g_lsx = S1 / lsx, g_lsp = S2 / lsp), the projection
+    backward over W' and its unfolding."""
+
+    @staticmethod
+    def forward(ctx, x, Wqx, bqx, Wkx, bkx, Wqp, bqp, Wkp, bkp, ovx, lsx, ovp, lsp, layer, g, norm_idx):
+        ns, m, rl = layer.scores_and_stats(g, x.detach(), norm_idx, fresh=True)
+        att = layer.edge_attention(g, ns, m, rl, norm_idx)
+        ctx.save_for_backward(x, ovx, lsx, ovp, lsp, att)
+        ctx.layer, ctx.g, ctx.norm_idx, ctx.ns = layer, g, norm_idx, ns
+        ctx.Wf = layer.wcat()[0]  # the folded operand these scores were projected with
+        ctx.sp = (rl, m.amax) if isinstance(m, ops.SquareplusState) else None
+        return att
+
+    @staticmethod
+    def backward(ctx, g_att):
+        x, ovx, lsx, ovp, lsp, att = ctx.saved_tensors
+        g, ns, norm_idx, lay = ctx.g, ctx.ns, ctx.norm_idx, ctx.layer
+        grouped = g.csr if norm_idx == 0 else g.csc
+        if ctx.sp is not None:
+            gs = ops.squareplus_backward(grouped, att, g_att.float(), *ctx.sp)
+        else:
+            gs = ops.softmax_backward(grouped, att, g_att.float())
+        gq, S0, S1, S2 = ops.score_grad_split(g.csr, 0, ns, gs, lay.d_k, with_params=True)
+        gk = ops.score_grad_split(g.csc, 1, ns, gs, lay.d_k)
+        gqk = torch.cat([gq, gk], 1)
+        xd = x.detach()
+        gx, _ = ops.linear(gqk, ctx.Wf.t().contiguous())       # gx = [g_q' | g_k'] W'
+        gW = ops.linear_wgrad(gqk, xd.reshape(g.R, -1))         # [4 att, C] = gqk^T x
+        gb = gqk.sum(0)
+        ovx, lsx, ovp, lsp = ovx.detach(), lsx.detach(), ovp.detach(), lsp.detach()
+        C, F, P = lay.beltrami_dims
+        gws = unfold_beltrami(gW, gb, lsx, lsp, lay.h, F, P, C)
+        scal = tuple((v.double() * s).to(v.dtype).reshape(v.shape) for v, s in
+                     ((ovp, S0), (1.0 / lsx, S1), (ovx, S0), (1.0 / lsp, S2)))
+        return (gx.view(x.shape),) + gws + scal + (None, None, None)
 
 
 class _MixProject(torch.autograd.Function):
@@ -342,15 +475,29 @@ class SpGraphTransAttentionLayer(nn.Module):
         self.d_k = self.attention_dim // self.h
         _check_supported(opt)
         self.mix = bool(opt.get('mix_features', False))
-        if opt.get('attention_type', 'scaled_dot') == "exp_kernel":
-            self.output_var = nn.Parameter(torch.ones(1))
-            self.lengthscale = nn.Parameter(torch.ones(1))
-        self.Q = nn.Linear(in_features, self.attention_dim)
-        self.init_weights(self.Q)
-        self.V = nn.Linear(in_features, self.attention_dim)
-        self.init_weights(self.V)
-        self.K = nn.Linear(in_features, self.attention_dim)
-        self.init_weights(self.K)
+        self.beltrami_kernel = beltrami_kernel(opt)
+        if self.beltrami_kernel:
+            # the product kernel (:90-107): split projections of the feature (+ label) and the
+            # positional columns, an amplitude and a lengthscale each; no Q, K or V
+            C, F, P = self.beltrami_dims = beltrami_widths(opt, in_features)
+            self.output_var_x = nn.Parameter(torch.ones(1))
+            self.lengthscale_x = nn.Parameter(torch.ones(1))
+            self.output_var_p = nn.Parameter(torch.ones(1))
+            self.lengthscale_p = nn.Parameter(torch.ones(1))
+            for name, width in (('Qx', C - P), ('Vx', C - P), ('Kx', C - P), ('Qp', P), ('Vp', P), ('Kp', P)):
+                lin = nn.Linear(width, self.attention_dim)
+                self.init_weights(lin)
+                setattr(self, name, lin)
+        else:
+            if opt.get('attention_type', 'scaled_dot') == "exp_kernel":
+                self.output_var = nn.Parameter(torch.ones(1))
+                self.lengthscale = nn.Parameter(torch.ones(1))
+            self.Q = nn.Linear(in_features, self.attention_dim)
+            self.init_weights(self.Q)
+            self.V = nn.Linear(in_features, self.attention_dim)
+            self.init_weights(self.V)
+            self.K = nn.Linear(in_features, self.attention_dim)
+            self.init_weights(self.K)
         self.activation = nn.Sigmoid()
         self.Wout = nn.Linear(self.d_k, in_features)
         self.init_weights(self.Wout)
@@ -358,6 +505,7 @@ class SpGraphTransAttentionLayer(nn.Module):
         self._graph_key = None
         self._uniform = None  # (graph, NodeScores, m, rl, csr weights) for the uniform fast path
         self._wcat = None     # (param versions, ([Wq;Wk], [bq;bk]))
+        self._p0 = None       # (param versions, ovx * ovp): the beltrami product kernel's amplitude
         self._sp_bufs = None  # (state shape, ops.SquareplusState): the squareplus operands
         self._mixp = None     # (param versions, (Wv, bv, Wout, b_out)): mix_features
         self._uniform_heads = None  # (graph, per-head weights [nnz, h]) of the uniform case: mix_features
@@ -371,7 +519,27 @@ class SpGraphTransAttentionLayer(nn.Module):
     def score_mode(self):
         return self.opt.get('attention_score_mode', 'reference')
 
+    def score_parameters(self):
+        """The parameters the scores depend on, in the order of the layer's autograd function
+        (what the transformer function and the blocks test for requires_grad)."""
+        if self.beltrami_kernel:
+            return (self.Qx.weight, self.Qx.bias, self.Kx.weight, self.Kx.bias, self.Qp.weight, self.Qp.bias,
+                    self.Kp.weight, self.Kp.bias, self.output_var_x, self.lengthscale_x, self.output_var_p,
+                    self.lengthscale_p)
+        ps = (self.Q.weight, self.Q.bias, self.K.weight, self.K.bias)
+        if self.opt.get('attention_type', 'scaled_dot') == 'exp_kernel':
+            ps += (self.output_var, self.lengthscale)
+        return ps
+
     def _score_params(self):
+        if self.beltrami_kernel:
+            # the folded projection carries the lengthscales: p0 = ovx ovp, p1 = 1.  The two
+            # amplitudes are read on the host once per parameter version (the eager step that
+            # precedes a capture reads them; a capture must not synchronise)
+            key = (_tensor_key(self.output_var_x), _tensor_key(self.output_var_p))
+            if self._p0 is None or self._p0[0] != key:
+                self._p0 = (key, float(self.output_var_x.detach()) * float(self.output_var_p.detach()))
+            return self._p0[1], 1.0
         if self.opt.get('attention_type', 'scaled_dot') == 'exp_kernel':
             # p0 = output_var, p1 = lengthscale: read once per call (host sync of 2 scalars)
             return float(self.output_var.detach()), float(self.lengthscale.detach())
@@ -466,7 +634,18 @@ class SpGraphTransAttentionLayer(nn.Module):
         return self.score_mode != 'reference' or self.opt.get('attention_type', 'scaled_dot') != 'scaled_dot'
 
     def wcat(self):
-        """([Wq; Wk], [bq; bk]) cached per parameter version."""
+        """([Wq; Wk], [bq; bk]) cached per parameter version; the beltrami product kernel:
+        the folded operand (fold_beltrami, [4 att, C]) over its eight tensors and two lengthscales."""
+        if self.beltrami_kernel:
+            ps = self.score_parameters()
+            ps = ps[:8] + (ps[9], ps[11])
+            key = tuple(_tensor_key(t) for t in ps)
+            if self._wcat is None or self._wcat[0] != key:
+                C, F, P = self.beltrami_dims
+                with torch.no_grad():
+                    W, b = fold_beltrami(*[t.detach() for t in ps], self.h, F, P, C)
+                self._wcat = (key, (W.contiguous(), b.contiguous()))
+            return self._wcat[1]
         key = tuple(_tensor_key(t) for t in (self.Q.weight, self.Q.bias, self.K.weight, self.K.bias))
         if self._wcat is None or self._wcat[0] != key:
             self._wcat = (key, (torch.cat([self.Q.weight.detach(), self.K.weight.detach()], 0).contiguous(),
@@ -475,6 +654,10 @@ class SpGraphTransAttentionLayer(nn.Module):
 
     def node_scores(self, g, x):
         p0, p1 = self._score_params()
+        if self.beltrami_kernel:
+            # exp_kernel over the folded projection: heads h, dk' = 2 dk (fold_beltrami)
+            return ops.node_scores(g, x, None, None, None, None, self.h, 'exp_kernel', self.score_mode, p0, p1,
+                                   wcat=self.wcat())
         wcat = self.wcat() if self.uses_wcat() else None
         return ops.node_scores(g, x, self.Q.weight.detach(), self.Q.bias.detach(), self.K.weight.detach(),
                                self.K.bias.detach(), self.h, self.opt.get('attention_type', 'scaled_dot'),
@@ -498,7 +681,12 @@ class SpGraphTransAttentionLayer(nn.Module):
         norm_idx = int(self.opt['attention_norm_idx'])
         ov = getattr(self, 'output_var', None)
         ls = getattr(self, 'lengthscale', None)
-        if _needs_grad(x, self.Q.weight, self.Q.bias, self.K.weight, self.K.bias, ov, ls):
+        if _needs_grad(x, *self.score_parameters()):
+            if self.beltrami_kernel:
+                if x.dtype != torch.float32:
+                    raise NotImplementedError("gnpde: gnpde_beltrami_kernel trains on fp32 states only (got %s)"
+                                              % x.dtype)
+                return _BeltramiAttention.apply(x, *self.score_parameters(), self, g, norm_idx)
             return _EdgeAttention.apply(x, self.Q.weight, self.Q.bias, self.K.weight, self.K.bias, ov, ls, self, g,
                                         norm_idx)
         ns, m, rl = self.scores_and_stats(g, x, norm_idx)
@@ -612,9 +800,7 @@ class ODEFuncTransformerAtt(ODEFunc):
         if lay.mix and x.dtype != torch.float32:
             raise NotImplementedError("gnpde: transformer mix_features runs on fp32 states only (got %s)" % x.dtype)
         mixp = (lay.V.weight, lay.V.bias, lay.Wout.weight, lay.Wout.bias) if lay.mix else ()
-        if stage is None and _needs_grad(x, self.alpha_train, self.beta_train, lay.Q.weight, lay.Q.bias,
-                                         lay.K.weight, lay.K.bias, getattr(lay, 'output_var', None),
-                                         getattr(lay, 'lengthscale', None), *mixp):
+        if stage is None and _needs_grad(x, self.alpha_train, self.beta_train, *lay.score_parameters(), *mixp):
             return self._rhs_autograd(g, x)
         norm_idx = int(self.opt['attention_norm_idx'])
         add_source = bool(self.opt.get('add_source', False))

@@ -1288,7 +1288,9 @@ def node_scores(g, x, Wq, bq, Wk, bk, heads, attention_type='scaled_dot', score_
     # mode's key sum and node scores read fp32
     bf = isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 and mode != _lib.SCORE_REFERENCE
     xr = _rows(x, "x", torch.bfloat16 if bf else torch.float32)
-    att = Wq.shape[0]
+    # a given [Wq; Wk] operand decides the width (the beltrami layer folds its four
+    # projections into one and has no Wq of its own)
+    att = Wq.shape[0] if Wq is not None else wcat[0].shape[0] // 2
     if att % heads:
         raise ValueError("attention_dim %d not divisible by heads %d" % (att, heads))
     dk = att // heads
@@ -2004,6 +2006,39 @@ def score_grad(grouped, side, ns, gs, with_params=False):
         return out, z, z
     gpd = gp[:grouped.nnz].double()
     return out, gpd[:, :ns.heads].sum(), gpd[:, ns.heads:].sum()
+
+
+def score_grad_split(grouped, side, ns, gs, dk_split, with_params=False):
+    """gnpde_score_grad_split_f32: score_grad's exp_kernel path for heads of two parts
+    (elements [0, dk_split) and [dk_split, dk) of each head; the beltrami product kernel
+    folded into one exp_kernel): dL/d(q) (side 0) or dL/d(k) (side 1) [R, att]; with_params
+    also the fp64 sums of the three per-edge columns -> (out, S0, S1, S2):
+    S0 = sum g_s 2 s / p0, S1 / S2 = sum g_s s |q - k|^2 / p1^2 over the first / second part."""
+    _require_gpu(gs, "score grad", torch.float32)
+    if ns.mode != _lib.SCORE_EXP_KERNEL:
+        raise ValueError("score_grad_split: exp_kernel scores only (mode %d)" % ns.mode)
+    dk_split = int(dk_split)
+    if not 0 <= dk_split <= ns.dk:
+        raise ValueError("score_grad_split: dk_split %d outside [0, dk = %d]" % (dk_split, ns.dk))
+    gs = gs.contiguous()
+    H = ns.heads
+    att = H * ns.dk
+    if gs.numel() != max(grouped.nnz, 0) * H:
+        raise ValueError("score_grad_split: gs holds %d values, expected nnz * heads = %d"
+                         % (gs.numel(), grouped.nnz * H))
+    dev = gs.device
+    out = torch.empty(grouped.R, att, dtype=torch.float32, device=dev)
+    gp = torch.empty(max(grouped.nnz, 1), 3 * H, dtype=torch.float32, device=dev) if with_params else None
+    _lib.call("gnpde_score_grad_split_f32", _ptr(grouped.rowptr), _ptr(grouped.col), _ptr(grouped.perm), grouped.R,
+              grouped.nnz, int(side), H, ns.dk, dk_split, _ptr(ns.q), _ptr(ns.k), ns.ldqk, ns.p0, ns.p1, _ptr(gs),
+              _ptr(out), att, _ptr(gp), _stream(dev))
+    if not with_params:
+        return out
+    if grouped.nnz == 0:
+        z = torch.zeros((), dtype=torch.float64, device=dev)
+        return out, z, z, z
+    sums = gp[:grouped.nnz].double().view(grouped.nnz, 3, H).sum(dim=(0, 2))
+    return out, sums[0], sums[1], sums[2]
 
 
 def gather_head(grouped, w, h, scale=1.0):

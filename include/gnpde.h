@@ -823,6 +823,20 @@ int gnpde_score_grad_f32(const int32_t* rowptr, const int32_t* col, const int32_
                          float score_p0, float score_p1, const float* gs, float* out, int64_t ldo, float* gp,
                          void* stream);
 
+/* gnpde_score_grad_f32's EXP_KERNEL path for heads made of two parts (the beltrami
+ * product kernel folded into one exp_kernel): elements [0, dk_split) and
+ * [dk_split, dk) of every head.  out as above (the gradient of the whole head); for gp !=
+ * NULL, gp [nnz, 3*heads] in COO order, the squared distance summed per part:
+ *   gp[e*3H + h]      = gs * 2 s / score_p0,
+ *   gp[e*3H + H + h]  = gs * s * |own - oth|^2 over the first part  / score_p1^2,
+ *   gp[e*3H + 2H + h] = gs * s * |own - oth|^2 over the second part / score_p1^2
+ * (the caller sums the columns; fixed order, no atomics: deterministic).  0 <= dk_split
+ * <= dk, attention_dim <= 1024.                                                          */
+int gnpde_score_grad_split_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t R, int64_t nnz,
+                               int side, int64_t heads, int64_t dk, int64_t dk_split, const float* q, const float* k,
+                               int64_t ldqk, float score_p0, float score_p1, const float* gs, float* out, int64_t ldo,
+                               float* gp, void* stream);
+
 /* ---- GAT attention function (function_GAT_attention.py: ODEFuncAtt, SpGraphAttentionLayer) ----
  * Node-score pairs sp [B*N, 2*heads] fp64 = [sl | sr] = x U, where U [C, 2*heads] is W
  * [C, att] (row-major) folded with a [2*dk] (dk = att / heads, the same a for every
