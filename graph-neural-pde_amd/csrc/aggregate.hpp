@@ -409,6 +409,78 @@ static __global__ __launch_bounds__(64) void dense_coef_kernel(gnpde_stage_epilo
   if (threadIdx.x == 0) dense_coefs(st, st.dense_tab);
 }
 
+// ------------------------------------------------------------------ frozen rows
+// A row whose only edge is its own self loop of weight exactly 1.0f, and that no other row
+// gathers, has f = a*(1*x - x) = 0: the first three rk4 stage inputs of such a row equal the
+// row bit for bit, nothing reads them, and the step changes the row only by the rounding of
+// its last combination, which depends on nothing but the row.  A solve
+// that reads its state only at the end then leaves these rows out of every launch but its
+// last, which streams them once: kFrozenPass row slices in flight per lane, each taken
+// through `steps` whole rk4 steps in registers — the aggregation of its one edge
+// (fmaf(1, v, 0)), f = a*(ax - x), and the SAME stage_combine / epi_finish as every other row
+// with the own row, the base and every operand set to the slice: the operation sequence, and
+// so the bits, of `steps` full steps (the last step's coefficients serve all: f is 0, or NaN
+// for a non-finite entry, whatever the step size).  A lane reads its slice of fz_home before
+// it stores (to the same row, or through out_rows).
+constexpr int kStgFrozen = 6;
+constexpr int kFrozenPass = 4;  // row slices in flight per lane
+template <int RPW>
+constexpr int frozen_rows_per_block() {
+  return kWavesPerBlock * RPW * kFrozenPass;
+}
+
+template <int VEC, int GL, int RPW>
+__device__ __forceinline__ void frozen_tail(const Epi& ep, int C, const float* __restrict__ home, int r0, int r1,
+                                            int steps, int tb, int wave, int rs, int gl) {
+  const int cc = gl * VEC;
+  const int rb = r0 + tb * frozen_rows_per_block<RPW>() + wave * RPW + rs;
+  Packed<VEC, float> v[kFrozenPass];
+#pragma unroll
+  for (int i = 0; i < kFrozenPass; ++i) {
+    const int row = rb + i * kWavesPerBlock * RPW;
+    if (row < r1 && rs < RPW && cc < C) {
+      load_packed<VEC>(home + (int64_t)row * ep.ldx + cc, v[i]);
+    } else {
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) v[i].d[t] = 0u;
+    }
+  }
+  const float a = (ep.flags & GNPDE_EPI_RHS) ? epi_alpha(ep) : 1.f;
+  // the steps before the last: epi_finish's arithmetic (EPI_RHS, no source, f_lin 0: launch_agg_frozen)
+  // without its stores, the slices of a lane side by side
+  const float sc = out_scale(ep.st, 0, stage_scale(ep.st));
+#pragma unroll 1
+  for (int k = 1; k < steps; ++k) {
+#pragma unroll
+    for (int i = 0; i < kFrozenPass; ++i) {
+      const Packed<VEC, float> x = v[i];
+      float o[VEC], r[VEC];
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) o[t] = a * (fmaf(1.0f, unpack(x, t), 0.f) - unpack(x, t));
+      auto kval = [&](int /*j*/, int t) -> float { return unpack(x, t); };
+      stage_combine<VEC, kStagePre, float>(ep, ep.st.o[0], 0, o, x, &x, kval, sc, r);
+      pack_into<VEC, float>(r, v[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kFrozenPass; ++i) {
+    const int row = rb + i * kWavesPerBlock * RPW;
+    if (row < r1 && rs < RPW && cc < C) {
+      EpiPre<VEC, float, 1> p;
+      p.xr = v[i];
+      p.x0r = v[i];
+#pragma unroll
+      for (int j = 0; j < stage_bpre<1>(); ++j) p.base[j] = v[i];
+#pragma unroll
+      for (int j = 0; j < stage_kpre<1>(); ++j) p.kv[j] = v[i];
+      float ax[VEC];
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) ax[t] = fmaf(1.0f, unpack(v[i], t), 0.f);
+      epi_finish<VEC, 1, float>(ep, row, cc, ax, a, 0.f, p, nullptr);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ aggregation kernel
 // Lane layout: RPW row slots of SL = 64/RPW lanes per wavefront (one plan item
 // each); inside a slot lane = g*GL + gl: G = SL/GL edges are gathered side by
@@ -421,10 +493,17 @@ static __global__ __launch_bounds__(64) void dense_coef_kernel(gnpde_stage_epilo
 // and whole pairs of half batches pipelined.  Hub rows are combined in-launch
 // by the chunk that arrives last (hub_claim), and run through the same
 // epilogue as whole rows.
-template <int VEC, int GL, int NCH, int U, int RPW, int STG, class WP, class T = float>
+//
+// STG_ = kStgFrozen (the last launch of an rk4 solve whose graph has frozen rows, DESIGN.md
+// §6.23): the epilogue of STG 1, and the workgroups behind those of the items stream the
+// frozen rows [fz_r0, fz_r1) — rows whose one edge is their own self loop of weight 1.0f,
+// gathered by no other row — from fz_home through fz_steps steps' epilogues (frozen_tail).
+template <int VEC, int GL, int NCH, int U, int RPW, int STG_, class WP, class T = float>
 __global__ __launch_bounds__(256) void agg_kernel(const int4* __restrict__ items, int n_items, int4* heavy,
                                                    int n_heavy, const int* __restrict__ col, WP wp, int C, Epi ep,
-                                                   float* __restrict__ partials) {
+                                                   float* __restrict__ partials, const float* fz_home = nullptr,
+                                                   int fz_r0 = 0, int fz_r1 = 0, int fz_steps = 1) {
+  constexpr int STG = STG_ == kStgFrozen ? 1 : STG_;
   constexpr int SL = kWave / RPW;
   constexpr int G = SL / GL;
   static_assert((SL & (SL - 1)) == 0 || G == 1, "non-power-of-two row slots hold one edge group");
@@ -432,6 +511,15 @@ __global__ __launch_bounds__(256) void agg_kernel(const int4* __restrict__ items
   const int lane = threadIdx.x & 63;
   const int rs = lane / SL, sl = lane % SL;
   const int g = sl / GL, gl = sl % GL;
+  if constexpr (STG_ == kStgFrozen) {
+    static_assert(NCH == 1 && G == 1 && sizeof(T) == 4, "the frozen tail is written for the headline geometry");
+    const int nb = (n_items + kWavesPerBlock * RPW - 1) / (kWavesPerBlock * RPW);  // the items' workgroups
+    if ((int)blockIdx.x >= nb) {  // workgroup-uniform
+      frozen_tail<VEC, GL, RPW>(ep, C, fz_home, fz_r0, fz_r1, fz_steps, (int)blockIdx.x - nb, threadIdx.x >> 6, rs,
+                                gl);
+      return;
+    }
+  }
   const int wid = uniform(xcd_block(ep.xcd_remap) * kWavesPerBlock + (threadIdx.x >> 6));
   const int item = wid * RPW + rs;
   if (wid * RPW >= n_items) return;
@@ -850,6 +938,35 @@ inline int epi_vec_width(const Epi& ep, int64_t C, const void* partials) {
     if (ok) return v;
   }
   return 1;
+}
+
+// The last launch of an rk4 solve with frozen rows (kStgFrozen): the plan's first n_items items
+// (the rows that are not frozen) and, behind their workgroups, the frozen rows [r0, r1) of
+// `home` taken through `steps` steps.  The headline geometry only — fp32 rows of 65-128
+// columns, 16-byte slices, the fixed-grid epilogue (STG 1) — anything else is the caller's
+// error: it keeps the full launch.
+// (A template so that only the translation unit that calls it instantiates the kernel.)
+template <class T = float>
+static int launch_agg_frozen(const int32_t* items, int64_t n_items, int32_t* heavy, int64_t n_heavy,
+                             const int32_t* col, const PlainWeights& wp, int64_t C, const Epi& ep, float* partials,
+                             const float* home, int64_t r0, int64_t r1, int64_t steps, hipStream_t s) {
+  constexpr int VEC = 4, GL = 32, RPW = 2;
+  const int64_t lanes = ceil_div(C, VEC);
+  GNPDE_REQUIRE(epi_vec_width<float>(ep, C, partials) == VEC && aligned16(home) && lanes > 16 && lanes <= GL,
+                GNPDE_EUNSUPPORTED, "spmm_rhs_frozen: fp32 rows of 65-128 columns in 16-byte slices only (C=%lld)",
+                (long long)C);
+  GNPDE_REQUIRE(epi_stage_kind(ep) == 1 && ep.st.n_out == 1 && !ep.st.f_out && !ep.st.dense_tab && ep.st.f_lin == 0.f &&
+                    !(ep.flags & GNPDE_ADD_SOURCE) && (ep.flags & GNPDE_EPI_RHS),
+                GNPDE_EUNSUPPORTED, "spmm_rhs_frozen: the fixed-grid stage epilogue of the source-free RHS only");
+  const unsigned grid = (unsigned)(ceil_div(n_items, (int64_t)kWavesPerBlock * RPW) +
+                                   ceil_div(r1 - r0, (int64_t)frozen_rows_per_block<RPW>()));
+  if (grid > 0) {
+    agg_kernel<VEC, GL, 1, 4, RPW, kStgFrozen, PlainWeights, float><<<grid, kBlock, 0, s>>>(
+        reinterpret_cast<const int4*>(items), (int)n_items, reinterpret_cast<int4*>(heavy), (int)n_heavy, col, wp,
+        (int)C, ep, partials, home, (int)r0, (int)r1, (int)steps);
+    GNPDE_LAUNCH_CHECK();
+  }
+  return GNPDE_OK;
 }
 
 template <class WP, class T = float>

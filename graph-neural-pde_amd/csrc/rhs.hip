@@ -21,6 +21,30 @@ int gnpde_spmm_rhs_f32(const int32_t* items, int64_t n_items, int32_t* heavy, in
   return launch_agg(items, n_items, heavy, n_heavy, col, wp, C, ep, partials, as_stream(stream));
 }
 
+int gnpde_spmm_rhs_frozen_f32(const int32_t* items, int64_t n_live_items, int32_t* heavy, int64_t n_heavy,
+                              const int32_t* col, const float* w, int64_t C, const float* x, int64_t ldx,
+                              const float* alpha, int flags, int64_t ldf, float* partials, int64_t n_slots,
+                              const gnpde_stage_epilogue_t* stage, const float* home, int64_t row0, int64_t row1,
+                              int64_t steps, void* stream) {
+  GNPDE_REQUIRE(stage != nullptr && home != nullptr, GNPDE_EINVAL, "spmm_rhs_frozen: NULL stage or home");
+  const Epi ep = make_epi(x, ldx, nullptr, 0, alpha, nullptr, flags, nullptr, ldf, stage);
+  int rc = check_epi(ep, C, n_heavy, partials, n_slots);
+  if (rc) return rc;
+  GNPDE_REQUIRE(n_live_items >= 0 && n_live_items < INT32_MAX && n_heavy >= 0, GNPDE_EINVAL,
+                "spmm_rhs_frozen: bad item counts");
+  GNPDE_REQUIRE(n_live_items == 0 || (items && col && w), GNPDE_EINVAL, "spmm_rhs_frozen: NULL plan/col/w");
+  GNPDE_REQUIRE(row0 >= 0 && row0 <= row1 && row1 < INT32_MAX && ldx == ldf, GNPDE_EINVAL,
+                "spmm_rhs_frozen: frozen rows [%lld, %lld) / leading dimensions", (long long)row0, (long long)row1);
+  GNPDE_REQUIRE(steps >= 1 && steps < INT32_MAX, GNPDE_EINVAL, "spmm_rhs_frozen: steps=%lld", (long long)steps);
+  // the frozen rows are read and written by the same lane; through out_rows they land elsewhere
+  for (int i = 0; i < stage->n_out; ++i)
+    GNPDE_REQUIRE(stage->out_rows == nullptr || stage->o[i].out != home, GNPDE_EINVAL,
+                  "spmm_rhs_frozen: output %d aliases the frozen rows' home under out_rows", i);
+  PlainWeights wp{w};
+  return launch_agg_frozen(items, n_live_items, heavy, n_heavy, col, wp, C, ep, partials, home, row0, row1, steps,
+                           as_stream(stream));
+}
+
 int gnpde_spmm_rhs_bf16(const int32_t* items, int64_t n_items, int32_t* heavy, int64_t n_heavy,
                         const int32_t* col, const float* w, int64_t C, const uint16_t* x, int64_t ldx,
                         const uint16_t* x0, int64_t ldx0, const float* alpha, const float* beta, int flags, uint16_t* f,

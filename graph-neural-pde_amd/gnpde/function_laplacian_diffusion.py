@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .base_classes import ODEFunc
+from .base_classes import ODEFunc, _tensor_key
 from .utils import MaxNFEException
 
 
@@ -82,6 +82,7 @@ class LaplacianODEFunc(ODEFunc):
         # (adjoint_direct_ok): forward() then hands autograd the detached weights, so its
         # vector-Jacobian products form no weight gradient (the SDDMM) only to drop it
         self.adjoint_const_weights = False
+        self._frozen_unit = None  # (key of the weights, whether every frozen row's weight is 1.0): frozen_rows
         if opt.get('multi_modal', False):
             if opt.get('gnpde_multi_modal', False):
                 raise NotImplementedError("gnpde: multi_modal with opt['gnpde_multi_modal'] is served by "
@@ -167,11 +168,34 @@ class LaplacianODEFunc(ODEFunc):
     # its dense output into the steps' last launch (integrator.DENSE_FOLD)
     fold_dense = True
 
-    def rhs_stage(self, t, x, stage, linear=False):
+    def frozen_rows(self, x):
+        """The ops.FrozenRows a fixed-grid rk4 solve of state ``x`` may leave out of its RHS
+        launches (gnpde.integrator), or None.  Called with the solve's
+        NodeLayout active: B = 1, fp32 rows of 65-128 columns (the K1 geometry that carries
+        the frozen tail), no source term, plain CSR-order weights, and every frozen row's
+        weight exactly 1.0 — decided on the device with one host read whenever the weights
+        were built or refreshed (their source's identity or version changed), never in a capture."""
+        lay = self._layout
+        fr = lay.frozen if lay is not None else None
+        C = x.shape[-1]
+        if (fr is None or x.dim() != 3 or x.shape[0] != 1 or x.dtype != torch.float32 or C % 4 or not 64 < C <= 128
+                or self.opt.get('add_source', False) or fr.n_rows - fr.n_live < ops.FROZEN_MIN_ROWS):
+            return None
+        w, tag = self._weights_tensor()
+        wc = self.csr_weights(self.graph_for(x), w, tag)
+        if not isinstance(wc, torch.Tensor):  # compacted sampled weights
+            return None
+        key = (id(fr), id(wc), _tensor_key(w))
+        if self._frozen_unit is None or self._frozen_unit[0] != key:
+            self._frozen_unit = (key, ops.frozen_weights_unit(fr, wc))
+        return fr if self._frozen_unit[1] else None
+
+    def rhs_stage(self, t, x, stage, linear=False, frozen=None):
         """forward(t, x) with the solver's stage combination fused into the K1
         epilogue (gnpde.integrator, no-grad fixed-grid solvers).  linear=True
         evaluates the linear part sigma(alpha)(A - I) x alone (no source term):
-        the adaptive solvers' affine stage derivatives (Stage.f_lin)."""
+        the adaptive solvers' affine stage derivatives (Stage.f_lin).
+        frozen: (ops.FrozenRows, home or None, steps), as ops.spmm_rhs takes it."""
         if self.nfe > self.opt["max_nfe"]:
             raise MaxNFEException
         self.nfe += 1
@@ -181,7 +205,7 @@ class LaplacianODEFunc(ODEFunc):
         x0 = self.stable_x0(x) if add_source else None
         ops.spmm_rhs(g, self.csr_weights(g, w, tag), x, x0=x0, alpha=self.alpha_train.detach(),
                      beta=self.beta_train.detach(), rhs=True, alpha_sigmoid=not self.opt.get('no_alpha_sigmoid', False),
-                     add_source=add_source, stage=stage)
+                     add_source=add_source, stage=stage, frozen=frozen)
 
     def forward(self, t, x):  # the t param is needed by the ODE solver.
         if self.nfe > self.opt["max_nfe"]:

@@ -154,7 +154,7 @@ def _fusable(func, y0, combine):
 RHS_PER_STEP = {'euler': 1, 'midpoint': 2, 'rk4': 4}
 
 
-def _fused_step(method, func, t0, dt, t1, y0, ws, out=None, out_rows=None, inplace=False):
+def _fused_step(method, func, t0, dt, t1, y0, ws, out=None, out_rows=None, inplace=False, frozen=None):
     """One grid step with the stage combinations fused into the RHS epilogues
     (gnpde_stage_epilogue_t): same arithmetic as _fixed_step, ~7 fewer passes
     over the state per rk4 step and no separate combine launches.  ``out``:
@@ -162,7 +162,10 @@ def _fused_step(method, func, t0, dt, t1, y0, ws, out=None, out_rows=None, inpla
     [R]): y1's row r is stored at row out_rows[r] of ``out`` (the last step of
     a solve run in a node renumbering writes the caller's numbering).
     ``inplace`` (rk4): the step in three live buffers — y1 overwrites y0 when no
-    ``out`` is given, and y0 is left alone otherwise; the same bits either way."""
+    ``out`` is given, and y0 is left alone otherwise; the same bits either way.
+    ``frozen`` (the in-place rk4 step, _frozen_rows): (ops.FrozenRows, None) leaves the
+    graph's frozen rows out of the step; (ops.FrozenRows, n), the solve's last step, also
+    takes them from y0 through the solve's n steps at once; the same bits again."""
     y0 = y0.contiguous()
     if method == 'euler':
         y1 = torch.empty_like(y0) if out is None else out
@@ -191,12 +194,22 @@ def _fused_step(method, func, t0, dt, t1, y0, ws, out=None, out_rows=None, inpla
             # operand).  Same combinations, same operand order: the same bits.
             a, b = ws.get('a', y0), ws.get('b', y0)
             y1 = y0 if out is None else out
-            func.rhs_stage(t0, y0, ops.Stage(outs=[(a, y0, 1.0, dt / 3.0, [])]))
-            func.rhs_stage(t0 + dt / 3.0, a, ops.Stage(outs=[(b, a, -1.0, dt, [(y0, 2.0)])]))
-            func.rhs_stage(t0 + dt * 2.0 / 3.0, b, ops.Stage(outs=[(a, b, -1.0, dt, [(a, 2.0)])]))
+            # Frozen rows (f = 0, gathered by no other row): their x2, x3, x4 equal y bit for bit,
+            # y1 depends on nothing but y, and nothing reads them before the solve's end.  Every
+            # launch leaves them out (their rows of y, a and b stay as they are) but the last of
+            # the solve, which takes them from y0 through all its ``steps`` steps in registers
+            # and stores them through out_rows.
+            fr, fsteps = frozen if frozen is not None else (None, None)
+            skip = {} if fr is None else {'frozen': (fr, None, 0)}
+            last = skip if fsteps is None else {'frozen': (fr, y0, fsteps)}
+            func.rhs_stage(t0, y0, ops.Stage(outs=[(a, y0, 1.0, dt / 3.0, [])]), **skip)
+            func.rhs_stage(t0 + dt / 3.0, a, ops.Stage(outs=[(b, a, -1.0, dt, [(y0, 2.0)])]), **skip)
+            func.rhs_stage(t0 + dt * 2.0 / 3.0, b, ops.Stage(outs=[(a, b, -1.0, dt, [(a, 2.0)])]), **skip)
             func.rhs_stage(t1, a, ops.Stage(outs=[(y1, a, 0.375, dt * 0.125, [(b, 0.75), (y0, -0.125)])],
-                                            out_rows=out_rows))
+                                            out_rows=out_rows), **last)
             return y1
+        if frozen is not None:
+            raise ValueError("frozen rows are left out of the in-place rk4 step only")
         x2, x3, x4 = ws.get('a', y0), ws.get('b', y0), ws.get('c', y0)
         y1 = torch.empty_like(y0) if out is None else out
         func.rhs_stage(t0, y0, ops.Stage(outs=[(x2, y0, 1.0, dt / 3.0, [])]))
@@ -250,6 +263,26 @@ RK4_INPLACE = os.environ.get('GNPDE_RK4_INPLACE', '1') != '0'
 
 def _steps_inplace(method, func, y):
     return RK4_INPLACE and method == 'rk4' and y.is_cuda and getattr(func, 'alloc_state', None) is None
+
+
+# A graph's frozen rows — one edge, their own self loop of weight exactly 1.0, gathered by no
+# other row: f = 0, and a step changes the row by the rounding of its last combination alone —
+# are left out of every launch of an in-place rk4 solve with a single output time but the
+# solve's last, which takes them through all the steps at once and stores them in the caller's
+# numbering (ops.FrozenRows): nothing reads the state's frozen rows in
+# between.  Results do not depend on it.  GNPDE_FROZEN_ROWS=0 runs every row through every launch.
+FROZEN_ROWS = os.environ.get('GNPDE_FROZEN_ROWS', '1') != '0'
+# how many solves left frozen rows out (tests assert the path was taken, not silently dropped)
+frozen_stats = {'solves': 0}
+
+
+def _frozen_rows(func, method, y, inplace, t_h, step_hook):
+    """The ops.FrozenRows this solve leaves out of its launches, or None.  Called with the
+    solve's NodeLayout active and outside any capture (the module may read the host once)."""
+    fn = getattr(func, 'frozen_rows', None)
+    if not (FROZEN_ROWS and fn is not None and inplace and method == 'rk4' and len(t_h) == 2 and step_hook is None):
+        return None
+    return fn(y)
 
 
 def _pow2_blocks(k, cap):
@@ -307,8 +340,9 @@ class _StepGraphs(object):
     scratch) is built by an eager call before anything is captured, so nothing
     synchronises inside a capture."""
 
-    def __init__(self, method, func, dt, pool, inplace=False):
+    def __init__(self, method, func, dt, pool, inplace=False, frozen=None):
         self.method, self.dt, self.pool, self.inplace = method, dt, pool, inplace
+        self.frozen = frozen  # the ops.FrozenRows the captured steps leave out, or None
         self.n_rhs = RHS_PER_STEP[method]
         self.graphs = {}
         self.mempool = None
@@ -323,7 +357,8 @@ class _StepGraphs(object):
             with torch.cuda.graph(g, pool=self.mempool):
                 for k in range(s):
                     if self.inplace:
-                        _fused_step(self.method, func, 0.0, self.dt, self.dt, bufs[p], ws, inplace=True)
+                        _fused_step(self.method, func, 0.0, self.dt, self.dt, bufs[p], ws, inplace=True,
+                                    frozen=(self.frozen, None) if self.frozen is not None else None)
                         continue
                     i = p ^ (k & 1)
                     _fused_step(self.method, func, 0.0, self.dt, self.dt, bufs[i], ws, out=bufs[1 - i])
@@ -812,6 +847,11 @@ def _solve_fused(func, y0, t_h, steps, method, graph, step_hook=None):
     if lay is not None:
         func._layout = lay
     try:
+        fz = None
+        if lay is not None and n >= 1 and steps[-1][1] == t_h[-1] and (n == 1 or steps[-2][1] < t_h[-1]):
+            fz = _frozen_rows(func, method, bufs[0], inplace, t_h, step_hook)
+        if fz is not None:
+            frozen_stats['solves'] += 1
         sg = None
         if graph and n >= 2:
             # the first step's dt; the captured graphs replay only runs of exactly this dt
@@ -820,10 +860,10 @@ def _solve_fused(func, y0, t_h, steps, method, graph, step_hook=None):
             dt0 = steps[0][1] - steps[0][0]
             hit = _GRAPH_CACHE.get(func) if key is not None else None
             if (hit is not None and hit[0] == key and hit[1].dt == dt0 and hit[1].pool is pool
-                    and hit[1].inplace == inplace):
+                    and hit[1].inplace == inplace and hit[1].frozen is fz):
                 sg = hit[1]
             else:
-                sg = _StepGraphs(method, func, dt0, pool, inplace)
+                sg = _StepGraphs(method, func, dt0, pool, inplace, fz)
                 if key is not None:
                     _GRAPH_CACHE[func] = (key, sg, state)
         p = 0      # the state is in bufs[p]
@@ -840,16 +880,18 @@ def _solve_fused(func, y0, t_h, steps, method, graph, step_hook=None):
             m = i
             while m < n - 1 and steps[m][1] < t_h[j]:
                 m += 1
-            p = _advance(func, method, steps, i, m, p, pool, sg, inplace)
+            p = _advance(func, method, steps, i, m, p, pool, sg, inplace, fz)
             ta, tb = steps[m]
             if m == n - 1 and j == len(t_h) - 1 and t_h[j] == tb:
                 # the last step writes the result in the caller's numbering
                 _fused_step(method, func, ta, tb - ta, tb, bufs[p], ws, out=sol[j],
-                            out_rows=lay.order32 if lay is not None else None, inplace=inplace)
+                            out_rows=lay.order32 if lay is not None else None, inplace=inplace,
+                            frozen=(fz, n) if fz is not None else None)
                 j += 1
                 break
             # an output time inside the step is interpolated from the state before it: that
             # step keeps its input (the ping-pong form)
+            assert fz is None  # (a solve that leaves frozen rows out reads its state at its last step only)
             p = _advance(func, method, steps, m, m + 1, p, pool, sg, inplace and t_h[j] == tb)
             ya, yb = bufs[1 - p], bufs[p]
             while j < len(t_h) and tb >= t_h[j]:
@@ -892,8 +934,9 @@ def _hooked_steps(func, method, steps, t_h, sol, lay, pool, sg, inplace, step_ho
         j += 1
 
 
-def _advance(func, method, steps, i, m, p, pool, sg, inplace=False):
-    """Run steps i .. m-1 from bufs[p] (``inplace``: in bufs[p]); returns the parity the state ends in.
+def _advance(func, method, steps, i, m, p, pool, sg, inplace=False, frozen=None):
+    """Run steps i .. m-1 from bufs[p] (``inplace``: in bufs[p]; ``frozen``: leaving the graph's
+    frozen rows out, _frozen_rows); returns the parity the state ends in.
     Steps of the captured dt go through block graphs (binary decomposition),
     others — and every step while the module is not warm or too close to its
     max_nfe — run eagerly (a MaxNFEException is then raised at the exact call)."""
@@ -913,7 +956,7 @@ def _advance(func, method, steps, i, m, p, pool, sg, inplace=False):
             for s in _pow2_blocks(k, GRAPH_BLOCK):
                 sg.graph(func, s, q)
                 q = sg.end(s, q)
-        if sg is not None and sg.warm and dt == sg.dt and sg.inplace == inplace:
+        if sg is not None and sg.warm and dt == sg.dt and sg.inplace == inplace and sg.frozen is frozen:
             k = 1
             while i + k < m and steps[i + k][1] - steps[i + k][0] == dt:
                 k += 1
@@ -923,7 +966,8 @@ def _advance(func, method, steps, i, m, p, pool, sg, inplace=False):
                 i += k
                 continue
         if inplace:
-            _fused_step(method, func, ta, dt, tb, bufs[p], ws, inplace=True)
+            _fused_step(method, func, ta, dt, tb, bufs[p], ws, inplace=True,
+                        frozen=(frozen, None) if frozen is not None else None)
         else:
             _fused_step(method, func, ta, dt, tb, bufs[p], ws, out=bufs[1 - p])
             p = 1 - p

@@ -436,6 +436,48 @@ LAYOUT_MIN_ROWS = 32768          # below this the state sits in L2 / the Infinit
 LAYOUT_MIN_BYTES = int(float(os.environ.get("GNPDE_LAYOUT_MIN_MB", 16)) * (1 << 20))
 
 
+# A solve leaves FROZEN rows out of its RHS launches (gnpde.integrator) when
+# the graph has at least this many of them; below it there is nothing to gain.
+FROZEN_MIN_ROWS = 1024
+
+
+def self_loop_only_rows(rowptr, col, R, nnz):
+    """bool [R]: the rows of a grouped CSR whose only edge is their own self loop (graph only:
+    whatever its weight).  With weight 1 such a row has f = a*(1*x - x) = 0."""
+    rp = rowptr.long()
+    ln = rp[1:] - rp[:-1]
+    if nnz == 0:
+        return torch.zeros(R, dtype=torch.bool, device=rowptr.device)
+    first = col[rp[:-1].clamp(max=nnz - 1)].long()
+    return (ln == 1) & (first == torch.arange(R, device=rowptr.device))
+
+
+def layout_order(deg, cand):
+    """The NodeLayout's order of each batch element's nodes: ``deg`` [B,N] in-degrees, ``cand``
+    [B,N] bool (self_loop_only_rows) -> the old local id at each new position.  In-degree
+    descending, stable; inside the in-degree-1 class the candidates come last — a candidate of
+    in-degree 1 is gathered by nothing but its own self loop, so with B = 1 and no row of
+    in-degree 0 these rows are the state's last rows [n_live, R) (FrozenRows)."""
+    key = -2 * deg.long() + (cand & (deg == 1)).long()
+    return torch.argsort(key, dim=1, stable=True)
+
+
+class FrozenRows(object):
+    """The frozen rows of a NodeLayout's graph (B = 1): rows [n_live, n_rows), each with one
+    edge, its own self loop, and in-degree 1 — no other row gathers them; their items are the
+    plan's items [n_live_items, n_items), and ``pos`` the CSR positions of their edges.
+    Graph-only: whether a solve may leave them out also needs every weight at ``pos`` to be
+    exactly 1.0 (frozen_weights_unit)."""
+
+    def __init__(self, plan, n_live, n_rows, n_live_items, pos):
+        self.plan, self.n_live, self.n_rows, self.n_live_items, self.pos = plan, n_live, n_rows, n_live_items, pos
+
+
+def frozen_weights_unit(fr, w_csr):
+    """True when every frozen row's CSR-order weight is exactly 1.0f (one host read)."""
+    return bool((w_csr.index_select(0, fr.pos) == 1.0).all())
+
+
 class NodeLayout(object):
     """In-degree numbering of a GraphCSR's nodes and the same graph relabelled.
 
@@ -450,7 +492,8 @@ class NodeLayout(object):
         B, N, R = g.B, g.N, g.R
         dev = g.edge_index.device
         deg = g.indeg.view(B, N).long()
-        local_order = torch.argsort(-deg, dim=1, stable=True)  # old local id at each new position
+        cand = self_loop_only_rows(g.csr.rowptr, g.csr.col, R, g.nnz).view(B, N)
+        local_order = layout_order(deg, cand)  # old local id at each new position
         base = (torch.arange(B, device=dev, dtype=torch.int64) * N).view(B, 1)
         self.order = (local_order + base).reshape(R)
         self.order32 = self.order.to(torch.int32)  # the stage epilogue's out_rows (last step of a solve)
@@ -461,6 +504,23 @@ class NodeLayout(object):
         eip = torch.gather(local_new, 1, ei.reshape(B, -1)).view(ei.shape)
         self.graph = GraphCSR(eip, N, chunk=g.chunk, validate=False)
         self.R = R
+        self.frozen = self._frozen_rows(deg, cand) if B == 1 else None
+
+    def _frozen_rows(self, deg, cand):
+        """The FrozenRows of the relabelled graph, or None: the self-loop-only rows nobody else
+        gathers must be the last rows (no row of in-degree 0 behind them) and their items the
+        last of the plan.  Two host reads, once per graph."""
+        R = self.R
+        tail = cand & (deg == 1)
+        nf, n0 = torch.stack([tail.sum(), (deg == 0).sum()]).tolist()
+        plan = self.graph.csr.plan
+        if nf == 0 or n0 != 0 or plan is None or plan.n_items < nf:
+            return None
+        it = plan.items[:plan.n_items * 4].view(-1, 4)[plan.n_items - nf:]
+        rows = torch.arange(R - nf, R, device=it.device, dtype=it.dtype)
+        if not bool(((it[:, 0] == rows) & (it[:, 3] < 0) & (it[:, 2] - it[:, 1] == 1)).all()):
+            return None
+        return FrozenRows(plan, R - nf, R, plan.n_items - nf, it[:, 1].long())
 
     def to_internal(self, y):
         """[B,N,C] (or [R,C]) in user order -> the same in internal order (new tensor)."""
@@ -795,7 +855,7 @@ def stage_apply(stage, f, x, like):
 
 
 def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoid=True, add_source=False,
-             out=None, transpose=False, stage=None):
+             out=None, transpose=False, stage=None, frozen=None):
     """K1: f = a*(A x - x) [+ b*x0] (or A x with rhs=False).  x [B,N,C] fp32, or
     bf16 storage (gnpde_spmm_rhs_bf16: x, x0, f and stage tensors bf16, sums in
     fp32).
@@ -806,7 +866,12 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
     (returns None).  The adaptive solvers' wide stages (Stage.wide) are fused
     with plain weights; with weights computed on the fly (RefDstWeights, GatWeights,
     RefDstSquareplusWeights) f is formed first and the stage applied in a second pass
-    (stage_apply)."""
+    (stage_apply).
+    frozen: (FrozenRows, home, steps) — a launch of an rk4 solve that leaves the graph's frozen
+    rows out: home None runs the plan's other items only (nothing reads the frozen rows'
+    stage inputs); home = the state the solve began with (the solve's last launch) also takes
+    the frozen rows of ``home`` through ``steps`` steps' stage epilogues
+    (gnpde_spmm_rhs_frozen_f32): the bits of ``steps`` full steps."""
     on_the_fly = (RefDstWeights, GatWeights, RefDstSquareplusWeights)
     if stage is not None and stage.wide and isinstance(w_csr, on_the_fly):
         f = spmm_rhs(g, w_csr, x, x0=x0, alpha=alpha, beta=beta, rhs=rhs, alpha_sigmoid=alpha_sigmoid,
@@ -841,6 +906,22 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
     epi = (C, _ptr(xr), C, _ptr(x0r), C, _ptr(a), _ptr(b), _flags(rhs, alpha_sigmoid, add_source), _ptr(out), C,
            _ptr(partials), plan.n_slots, st, _stream(dev))
     items, col = plan.items, grouped.col
+    if frozen is not None:
+        fr, home, steps = frozen
+        if (fr.plan is not plan or stage is None or dt != torch.float32 or not isinstance(w_csr, torch.Tensor)
+                or add_source or not rhs):
+            raise ValueError("spmm_rhs: frozen rows take the plain-weight fp32 stage launches of their own graph")
+        if home is None:
+            _lib.call("gnpde_spmm_rhs_f32", _ptr(items), fr.n_live_items, _ptr(plan.heavy), plan.n_heavy,
+                      _ptr(col), _ptr(w_csr), *epi)
+        else:
+            hr = _rows(home, "frozen home", dt)
+            if hr.shape != xr.shape:
+                raise ValueError("spmm_rhs: the frozen rows' home must be shaped like x")
+            _lib.call("gnpde_spmm_rhs_frozen_f32", _ptr(items), fr.n_live_items, _ptr(plan.heavy), plan.n_heavy,
+                      _ptr(col), _ptr(w_csr), C, _ptr(xr), C, _ptr(a), _flags(rhs, alpha_sigmoid, add_source), C,
+                      _ptr(partials), plan.n_slots, st, _ptr(hr), fr.n_live, fr.n_rows, int(steps), _stream(dev))
+        return None
     if isinstance(w_csr, CompactWeights):  # the sampled graph: the plan's items over the retained edges
         if w_csr.grouped is not grouped or w_csr.transpose != bool(transpose):
             raise ValueError("spmm_rhs: compacted weights of another grouped CSR")

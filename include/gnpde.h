@@ -352,6 +352,30 @@ int gnpde_spmm_rhs_f32(const int32_t* items, int64_t n_items, int32_t* heavy, in
                        float* f, int64_t ldf, float* partials, int64_t n_slots,
                        const gnpde_stage_epilogue_t* stage, void* stream);
 
+/* The last K1 launch of an rk4 solve over a graph with FROZEN rows: rows whose only
+ * edge is their own self loop of weight exactly 1.0f and that no other row gathers
+ * (f = a*(1*x - x) = 0, so a step changes the row by the rounding of its last
+ * combination alone, which reads nothing but the row; the caller classifies them
+ * and numbers them last: rows [row0, row1), their items behind the plan's first
+ * n_live_items, and leaves them out of every earlier launch of the solve by
+ * passing gnpde_spmm_rhs_f32 the first n_live_items items only).  This launch runs
+ * the first n_live_items items as gnpde_spmm_rhs_f32 does and, behind them, streams
+ * the frozen rows from `home` [.., ldx] — the state the solve began with — through
+ * `steps` >= 1 steps' stage epilogues with the own row, the base and every k operand
+ * set to the row: the bits of `steps` full steps, every one with this stage's
+ * coefficients (f is 0, or NaN for a non-finite entry, whatever the step size; the
+ * steps of a solve share the sign of dt).  `home` may be the stage's output (in
+ * place: a lane reads its slice before it stores), but not under out_rows.  fp32
+ * rows of 65-128 columns in 16-byte slices, GNPDE_EPI_RHS without GNPDE_ADD_SOURCE,
+ * a fixed-grid stage (one output, no f_out, at most two k operands, f_lin 0, no
+ * dot / error / dense term); GNPDE_EUNSUPPORTED otherwise.  Other arguments as
+ * gnpde_spmm_rhs_f32.                                                         */
+int gnpde_spmm_rhs_frozen_f32(const int32_t* items, int64_t n_live_items, int32_t* heavy, int64_t n_heavy,
+                              const int32_t* col, const float* w, int64_t C, const float* x, int64_t ldx,
+                              const float* alpha, int flags, int64_t ldf, float* partials, int64_t n_slots,
+                              const gnpde_stage_epilogue_t* stage, const float* home, int64_t row0, int64_t row1,
+                              int64_t steps, void* stream);
+
 /* K1 on bfloat16 storage (configs[3], BLEND in bf16): x, x0, f and every
  * stage pointer of `stage` address bf16 arrays (raw uint16 bits; the stage
  * struct's float* fields are reinterpreted); weights, alpha, beta and the

@@ -1,17 +1,21 @@
 #!/usr/bin/env python
 """Per-stage times of the headline K1 in a rocprofv3 kernel trace of
 `bench.py --gpus 1 --steps K --warmup W`: the last 4 K dispatches of the fused-stage
-kernel are the timed solve's, four per rk4 step in stage order.
+kernel (and of its frozen-tail form, a step's last launch) are the timed solve's, four
+per rk4 step in stage order.
 python tools/k1_stage_times.py <run_kernel_trace.csv> [K]"""
 import csv
 import statistics
 import sys
 
 NAME = "void gnpde::agg_kernel<4, 32, 1, 4, 2, 1, gnpde::PlainWeights, float>"
+# a step's last launch on a graph with frozen rows (kStgFrozen)
+NAME_FROZEN = "void gnpde::agg_kernel<4, 32, 1, 4, 2, 6, gnpde::PlainWeights, float>"
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if r["Kernel_Name"].startswith(NAME))
+ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows
+            if r["Kernel_Name"].startswith((NAME, NAME_FROZEN)))
 print("K1 fused-stage dispatches: %d | name: %s" % (len(ev), NAME))
 ev = ev[-4 * steps:]
 for s in range(4):

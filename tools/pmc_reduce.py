@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Per-kernel HBM traffic of the tools/pmc_run.py workloads -> profiles/traffic.json.
 
-  tools/pmc_reduce.py TAG DIR [OUT.json]   (default profiles/traffic.json)
+  tools/pmc_reduce.py TAG DIR [OUT.json [BASE.json]]   (default profiles/traffic.json)
+
+BASE.json: an earlier result whose workloads are carried over where DIR has none
+(marked ``carried_from``), for a change that touches the kernels of one workload only.
 
 DIR holds, per workload W (':' written as '_'), W.json (the runner's JSON line)
 and the two rocprofv3 passes W_FETCH_SIZE/run_counter_collection.csv and
@@ -83,6 +86,14 @@ def main():
         out["workloads"][meta["workload"]] = ent
         print("%-24s" % meta["workload"], ", ".join("%s x%d %.1f MB" % (k["kernel"][:50], k["count"], k["bytes"] / 1e6)
                                                    for k in ks[:6]))
+    if len(sys.argv) > 4:
+        # workloads DIR does not hold are carried over from an earlier file, each marked with
+        # the tag and build it was measured at (their kernels must not have changed since)
+        base = json.load(open(sys.argv[4]))
+        for w, ent in base.get("workloads", {}).items():
+            if w not in out["workloads"]:
+                ent.setdefault("carried_from", {"tag": base.get("tag"), "build_id": base.get("build_id")})
+                out["workloads"][w] = ent
     path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "traffic.json")
     with open(path, "w") as fh:
         json.dump(out, fh, indent=1)
