@@ -11,6 +11,7 @@ from .block_constant import ConstantODEblock  # noqa: F401
 from .block_mixed import MixedODEblock  # noqa: F401
 from .block_transformer_hard_attention import HardAttODEblock  # noqa: F401
 from .block_transformer_attention import AttODEblock  # noqa: F401
+from .block_transformer_rewiring import RewireAttODEblock  # noqa: F401
 from .function_GAT_attention import ODEFuncAtt, SpGraphAttentionLayer  # noqa: F401
 from .function_laplacian_diffusion import LaplacianODEFunc  # noqa: F401
 from .function_laplacian_multimodal import MultiModalLaplacianODEFunc  # noqa: F401

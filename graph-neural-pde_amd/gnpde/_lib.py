@@ -180,6 +180,11 @@ SIGNATURES = {
     "gnpde_adams_workspace_bytes": (_size, []),
     "gnpde_adams_status_reset": (_int, [_vp, _vp]),
     "gnpde_adams_correct_f32": (_int, [_i64, _vp, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _size, _vp]),
+    "gnpde_two_hop_lds_max": (_int, []),
+    "gnpde_coalesce_sum_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "gnpde_two_hop_bound_i32": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "gnpde_two_hop_count_i32": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "gnpde_two_hop_fill_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 # constants mirrored from include/gnpde.h

@@ -8,13 +8,15 @@ Built here: block 'constant', 'attention', 'mixed',
 naming the key (the plain dict's behaviour is pinned by the host tests until the
 switch becomes the default).  'laplacian' with ``multi_modal`` and
 ``gnpde_multi_modal`` both set is function_laplacian_multimodal.MultiModalLaplacianODEFunc
-(the second modality's cross-attention; block 'constant' only).  Block 'rewire_attention' is out of scope and raises
-NotImplementedError naming the reason, rather than silently falling back to a
-different model.
+(the second modality's cross-attention; block 'constant' only).  Block 'rewire_attention'
+(block_transformer_rewiring.RewireAttODEblock) is returned when the option dict sets
+``gnpde_rewire_attention`` to a true value; without the key it raises NotImplementedError
+naming the key, rather than silently falling back to a different model.
 """
 from .block_constant import ConstantODEblock
 from .block_mixed import MixedODEblock
 from .block_transformer_hard_attention import HardAttODEblock
+from .block_transformer_rewiring import RewireAttODEblock
 from .block_transformer_attention import AttODEblock
 from .function_laplacian_diffusion import LaplacianODEFunc
 from .function_laplacian_multimodal import MultiModalLaplacianODEFunc
@@ -30,11 +32,6 @@ class FunctionNotDefined(Exception):
     pass
 
 
-_PENDING_BLOCKS = {
-    'rewire_attention': 'out of scope (graph surgery between forwards, SURVEY §2 row 9)',
-}
-
-
 def set_block(opt):
     ode_str = opt['block']
     if ode_str == 'mixed':
@@ -45,8 +42,11 @@ def set_block(opt):
         return HardAttODEblock
     if ode_str == 'constant':
         return ConstantODEblock
-    if ode_str in _PENDING_BLOCKS:
-        raise NotImplementedError("gnpde: block %r is %s" % (ode_str, _PENDING_BLOCKS[ode_str]))
+    if ode_str == 'rewire_attention':
+        if opt.get('gnpde_rewire_attention'):
+            return RewireAttODEblock
+        raise NotImplementedError("gnpde: block 'rewire_attention' (block_transformer_rewiring.RewireAttODEblock) is "
+                                  "opt-in: set opt['gnpde_rewire_attention'] = True to select it")
     raise BlockNotDefined
 
 

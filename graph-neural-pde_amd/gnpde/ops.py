@@ -2523,3 +2523,196 @@ def cross_attention(q, k, v, scale, lse=False, out=None):
               _ptr(ls), _stream(dev))
     out = out.view(shape)
     return (out, ls.view(shape[:-1])) if lse else out
+
+
+# --------------------------------------------------------------------------- two-hop product (rewire_attention)
+TWO_HOP_LDS_MAX = 512          # rows whose width bound fits the LDS hash table (csrc/two_hop.hip kThList)
+TWO_HOP_SCRATCH_BYTES = 1 << 28  # global scratch of the wide rows: one accumulator + bitmap per resident wavefront
+TWO_HOP_MAX_WAVES = 1024       # resident wavefronts of the wide-row regime
+TWO_HOP_DENSE_N = 2048         # two_hop_torch: the dense route up to this many nodes
+
+
+def _two_hop_coo(g_or_csr, w, num_nodes, name):
+    """(N, row int64 [E], col int64 [E], w [E]) of any accepted input: a GraphCSR
+    or an edge_index ([1,2,E] / [2,E], with num_nodes) with COO-order weights, or a coalesced
+    CSR (rowptr, col) with CSR-order values."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("%s: w must be a torch.Tensor" % name)
+    if isinstance(g_or_csr, GraphCSR):
+        ei, N = g_or_csr.edge_index, g_or_csr.N
+    elif isinstance(g_or_csr, torch.Tensor):
+        if num_nodes is None:
+            raise ValueError("%s: an edge_index needs num_nodes" % name)
+        ei, N = g_or_csr, int(num_nodes)
+    elif isinstance(g_or_csr, (tuple, list)) and len(g_or_csr) == 2:
+        rowptr, col = g_or_csr
+        N = rowptr.numel() - 1
+        nnz = w.numel()
+        if col.numel() < nnz:
+            raise ValueError("%s: %d values for %d columns" % (name, nnz, col.numel()))
+        row = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=rowptr.device),
+                                      (rowptr[1:] - rowptr[:-1]).long())
+        if row.numel() != nnz:
+            raise ValueError("%s: rowptr covers %d positions, w has %d" % (name, row.numel(), nnz))
+        return N, row, col[:nnz].long(), w.reshape(-1)
+    else:
+        raise TypeError("%s: expected a GraphCSR, an edge_index or a (rowptr, col) pair" % name)
+    if ei.dim() == 2:
+        ei = ei.unsqueeze(0)
+    if ei.dim() != 3 or ei.shape[1] != 2:
+        raise ValueError("%s: edge_index must be [1,2,E] or [2,E], got %s" % (name, tuple(ei.shape)))
+    if ei.shape[0] != 1:
+        raise NotImplementedError("gnpde: %s: the product's edge count differs per graph; only B = 1 is supported"
+                                  % name)
+    if w.numel() != ei.shape[2]:
+        raise ValueError("%s: %d weights for %d edges" % (name, w.numel(), ei.shape[2]))
+    return N, ei[0, 0], ei[0, 1], w.reshape(-1)
+
+
+def two_hop_torch(g_or_csr, w, num_nodes=None, dense_n=None):
+    """two_hop restated in torch ops (any device): the function the host tests check against
+    the oracle and the baseline of tools/rewire_bench.py.  Same contract: the structural
+    positions of W·W in ascending (row, col) order, S = 0.5 W + 0.5 W·W on them with a zero
+    diagonal, (edge_index int64 [1,2,nnz], values [nnz], rowptr int32 [N+1]).  Up to dense_n
+    (TWO_HOP_DENSE_N) nodes it densifies as the reference does; beyond, torch.sparse.mm and
+    coalesce.  The summation order is torch's, not the kernel's."""
+    N, row, col, wv = _two_hop_coo(g_or_csr, w, num_nodes, "two_hop_torch")
+    dev = wv.device
+    row, col = row.to(dev), col.to(dev)
+    if N <= int(TWO_HOP_DENSE_N if dense_n is None else dense_n):
+        W = torch.zeros(N, N, dtype=wv.dtype, device=dev).index_put_((row, col), wv, accumulate=True)
+        A = torch.zeros(N, N, dtype=torch.float64, device=dev).index_put_((row, col), torch.ones((), dtype=torch.float64,
+                                                                                                device=dev))
+        pos = torch.nonzero(torch.matmul(A, A) > 0)          # row-major: ascending (row, col)
+        S = 0.5 * W + 0.5 * torch.matmul(W, W)
+        S.fill_diagonal_(0)
+        r, c = pos[:, 0], pos[:, 1]
+        vals = S[r, c]
+    else:
+        Wc = torch.sparse_coo_tensor(torch.stack([row, col]), wv, (N, N)).coalesce()
+        WW = torch.sparse.mm(Wc, Wc).coalesce()
+        r, c = WW.indices()[0], WW.indices()[1]
+        vals = 0.5 * WW.values()
+        kww = r * N + c
+        kw = Wc.indices()[0] * N + Wc.indices()[1]
+        at = torch.searchsorted(kww, kw).clamp(max=max(kww.numel() - 1, 0))
+        hit = (kww[at] == kw) if kww.numel() else torch.zeros_like(kw, dtype=torch.bool)
+        vals[at[hit]] += 0.5 * Wc.values()[hit]              # W is coalesced: every position at most once
+        vals = torch.where(r == c, torch.zeros_like(vals), vals)
+    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), 0)
+    return torch.stack([r, c]).unsqueeze(0), vals, rowptr.to(torch.int32)
+
+
+def coalesced_csr(g, w):
+    """The coalesced CSR of a GraphCSR g (B = 1) with COO-order weights w: (rowptr int32
+    [N+1], col int32, val fp32), rows sorted by column, duplicates summed one after another in
+    COO order (gnpde_coalesce_sum_f32).  col / val keep the capacity of g's edge count (the
+    coalesced length is rowptr[N], on the device): nothing is read back."""
+    _require_gpu(w, "weights", torch.float32)
+    if g.B != 1:
+        raise NotImplementedError("gnpde: coalesced_csr: only B = 1 is supported")
+    csr, N, E = g.csr, g.N, g.nnz
+    dev = w.device
+    if w.numel() != E:
+        raise ValueError("coalesced_csr: %d weights for %d edges" % (w.numel(), E))
+    if E == 0:
+        return (torch.zeros(N + 1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                torch.zeros(1, dtype=torch.float32, device=dev))
+    key = csr.rowidx[:E].long() * N + csr.col[:E].long()
+    skey, order = torch.sort(key, stable=True)     # equal (row, col) keep their CSR (= COO) order
+    ws = w.reshape(-1)[csr.perm[:E].long()][order].contiguous()
+    first = torch.ones(E, dtype=torch.bool, device=dev)
+    first[1:] = skey[1:] != skey[:-1]
+    csum = torch.cumsum(first, 0)
+    uid = (csum - 1).contiguous()
+    col = torch.zeros(E, dtype=torch.int32, device=dev)
+    col[uid] = (skey % N).to(torch.int32)          # the entries of a run write the same value
+    val = torch.zeros(E, dtype=torch.float32, device=dev)
+    first8 = first.to(torch.uint8)
+    _lib.call("gnpde_coalesce_sum_f32", _ptr(ws), _ptr(first8), _ptr(uid), E, _ptr(val), _stream(dev))
+    before = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), csum])   # runs that start before position p
+    rowptr = before[csr.rowptr.long()].to(torch.int32).contiguous()             # a row's positions stay its own
+    return rowptr, col, val
+
+
+def two_hop_check_length(nnz):
+    """The product's length, checked before anything of that length is allocated."""
+    if nnz >= 2 ** 31:
+        raise ValueError("two_hop: the product has %d positions, the int32 CSR holds fewer than 2^31" % nnz)
+    return nnz
+
+
+def two_hop(g_or_csr, w, num_nodes=None, lds_max=None, scratch_bytes=None, return_col=False):
+    """The two-hop product of the rewire_attention block (csrc/two_hop.hip): for W given as a
+    GraphCSR or an edge_index ([1,2,E] / [2,E] int64 with num_nodes) with COO-order fp32 weights
+    (duplicates are summed: coalesced_csr), or as an already coalesced CSR (rowptr, col) with
+    CSR-order values, the structural positions of W·W in ascending (row, col) order and
+      S[i, j] = 0.5 * ((sum_m W[i, m] W[m, j]) + W[i, j]),  S[i, i] = 0
+    on them.  Returns (edge_index int64 [1,2,nnz], values fp32 [nnz], rowptr int32 [N+1])
+    (and the int32 columns with return_col).  Deterministic: the sum runs over the m of row i
+    in CSR order, no floating-point atomic.  Regimes: rows whose width bound ub_i = sum of the
+    neighbour rows' lengths is at most lds_max (default TWO_HOP_LDS_MAX, the largest value)
+    accumulate in an LDS hash table; wider rows in a dense accumulator in global scratch, one
+    per resident wavefront, as many as fit scratch_bytes (TWO_HOP_SCRATCH_BYTES).  One device
+    read: the product's length, to allocate it; 2^31 positions or more raise ValueError.  (An
+    edge_index or a (rowptr, col) pair is range-checked first, which reads the device too; a
+    GraphCSR was checked when it was built.)"""
+    if isinstance(w, torch.Tensor) and w.dtype != torch.float32:
+        raise TypeError("gnpde: two_hop: the weights must be torch.float32, got %s" % w.dtype)
+    if isinstance(g_or_csr, (tuple, list)) and len(g_or_csr) == 2:
+        rowptr, col = g_or_csr
+        _require_gpu(rowptr, "rowptr", torch.int32)
+        _require_gpu(col, "col", torch.int32)
+        _require_gpu(w, "values", torch.float32)
+        rowptr, col, val = rowptr.contiguous(), col.contiguous(), w.contiguous().reshape(-1)
+        N = rowptr.numel() - 1
+        if val.numel():
+            lo, hi = int(col[:val.numel()].min()), int(col[:val.numel()].max())
+            if lo < 0 or hi >= N or int(rowptr[-1]) != val.numel():
+                raise IndexError("two_hop: CSR columns must be in [0, %d) and rowptr[N] the value count" % N)
+    else:
+        if not isinstance(w, torch.Tensor):
+            raise TypeError("two_hop: w must be a torch.Tensor")
+        _require_gpu(w, "weights", torch.float32)
+        if isinstance(g_or_csr, torch.Tensor):
+            N0, r, c, _ = _two_hop_coo(g_or_csr, w, num_nodes, "two_hop")
+            g = GraphCSR(torch.stack([r, c]).unsqueeze(0), N0)
+        elif isinstance(g_or_csr, GraphCSR):
+            g = g_or_csr
+            _two_hop_coo(g, w, None, "two_hop")
+        else:
+            raise TypeError("two_hop: expected a GraphCSR, an edge_index or a (rowptr, col) pair")
+        rowptr, col, val = coalesced_csr(g, w.contiguous())
+        N = g.N
+    dev = val.device
+    cap = int(_lib.fn("gnpde_two_hop_lds_max")())
+    lds_max = TWO_HOP_LDS_MAX if lds_max is None else int(lds_max)
+    if not 0 <= lds_max <= cap:
+        raise ValueError("two_hop: lds_max=%d must be in [0, %d]" % (lds_max, cap))
+    if N == 0:
+        out = (torch.zeros(1, 2, 0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+               torch.zeros(1, dtype=torch.int32, device=dev))
+        return out + (torch.zeros(0, dtype=torch.int32, device=dev),) if return_col else out
+    words = (N + 31) // 32
+    budget = TWO_HOP_SCRATCH_BYTES if scratch_bytes is None else int(scratch_bytes)
+    n_waves = max(1, min(TWO_HOP_MAX_WAVES, budget // (4 * (N + words))))
+    acc = torch.empty(n_waves * N, dtype=torch.float32, device=dev)
+    bits = torch.zeros(n_waves * words, dtype=torch.int32, device=dev)
+    ub = torch.empty(N, dtype=torch.int32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    st = _stream(dev)
+    _lib.call("gnpde_two_hop_bound_i32", _ptr(rowptr), _ptr(col), N, _ptr(ub), st)
+    _lib.call("gnpde_two_hop_count_i32", _ptr(rowptr), _ptr(col), N, _ptr(ub), lds_max, n_waves, _ptr(acc), _ptr(bits),
+              _ptr(count), st)
+    ptr64 = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    ptr64[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+    nnz = two_hop_check_length(int(ptr64[-1]))  # the one device read: the product's length
+    out_ptr = ptr64.to(torch.int32)
+    out_col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    out_val = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+    out_ei = torch.empty(1, 2, nnz, dtype=torch.int64, device=dev)
+    _lib.call("gnpde_two_hop_fill_f32", _ptr(rowptr), _ptr(col), _ptr(val), N, _ptr(ub), lds_max, n_waves, _ptr(acc),
+              _ptr(bits), _ptr(out_ptr), nnz, _ptr(out_col), _ptr(out_val), _ptr(out_ei), st)
+    out = (out_ei, out_val[:nnz], out_ptr)
+    return out + (out_col[:nnz],) if return_col else out

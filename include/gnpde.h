@@ -1033,6 +1033,38 @@ int gnpde_adams_status_reset(void* workspace, void* stream);
 int gnpde_adams_correct_f32(int64_t n, const float* f, const float* delta, const float* y0, double cf, double rtol,
                             double atol, float* dy, float* x, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The two-hop product of the rewire_attention block (gnpde.block_transformer_rewiring,
+ * src/block_transformer_rewiring.py:65-93; entry points added under ABI 8).  W is a
+ * COALESCED CSR of N rows: int32 rowptr [N+1] and col (values in [0, N), ascending inside
+ * a row, no duplicates — caller-validated), fp32 val.  The product's positions are the
+ * structural non-zeros of W·W (some m with (i, m) and (m, j) stored), in ascending
+ * (row, column) order, each once, the diagonal included; their values
+ *   S[i, j] = 0.5 * ((sum_m W[i, m] W[m, j]) + W[i, j]),   S[i, i] = 0,
+ * the sum an fma chain over the m of row i in CSR order, W[i, j] added after it, the
+ * halving exact: no floating-point atomic, the same bits on every call.
+ *
+ * gnpde_coalesce_sum_f32 (the prep pass): w_sorted [E] in (row, column) order, first[p] = 1
+ * where p starts a run of equal (row, column), uid[p] = the run's index; out[uid] = the run's
+ * sum, its entries added one after another in that order.
+ * gnpde_two_hop_bound_i32: ub[i] = sum over the m of row i of len(row m), the upper bound of
+ * row i's width that selects its regime: 0 nothing, <= lds_max a hash table in LDS
+ * (lds_max <= gnpde_two_hop_lds_max()), beyond it a dense accumulator acc [n_waves * N] fp32
+ * and a bitmap bits [n_waves * ceil(N / 32)] (ZERO on entry, zero again on return) in global
+ * scratch, one slice per resident wavefront (1 <= n_waves <= 65536).
+ * gnpde_two_hop_count_i32 (symbolic): count[i] = positions of row i.  The caller forms
+ * out_ptr [N+1], the exclusive scan, and nnz_out = out_ptr[N] < 2^31.
+ * gnpde_two_hop_fill_f32 (numeric): out_col / out_val [nnz_out] and the COO list
+ * out_ei [2, nnz_out] (int64) in the same order.  ub, lds_max as in the symbolic pass.    */
+int gnpde_two_hop_lds_max(void);
+int gnpde_coalesce_sum_f32(const float* w_sorted, const uint8_t* first, const int64_t* uid, int64_t E, float* out,
+                           void* stream);
+int gnpde_two_hop_bound_i32(const int32_t* rowptr, const int32_t* col, int64_t N, int32_t* ub, void* stream);
+int gnpde_two_hop_count_i32(const int32_t* rowptr, const int32_t* col, int64_t N, const int32_t* ub, int64_t lds_max,
+                            int64_t n_waves, float* acc, uint32_t* bits, int32_t* count, void* stream);
+int gnpde_two_hop_fill_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, const int32_t* ub,
+                           int64_t lds_max, int64_t n_waves, float* acc, uint32_t* bits, const int32_t* out_ptr,
+                           int64_t nnz_out, int32_t* out_col, float* out_val, int64_t* out_ei, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
