@@ -481,6 +481,189 @@ __device__ __forceinline__ void frozen_tail(const Epi& ep, int C, const float* _
   }
 }
 
+// ------------------------------------------------------------------ column stripes
+// The headline geometry (plain weights, fp32 rows of 65-128 columns in 16-byte slices, stage
+// kinds 0 and 1) on a graph whose gathered rows do not fit one XCD's L2: the
+// eight L2s are not shared and every XCD runs a random eighth of the items, so every XCD pulls
+// nearly every gathered row once per launch.  With S column stripes a workgroup aggregates
+// 128 / S columns of ALL its rows — 32 / S lanes per row slot, 2 S slots per wavefront — and
+// workgroup b takes stripe (b % 8) * S / 8: the workgroups of 8 / S XCDs (b % 8 says which
+// workgroups share an XCD: an observation, used for speed only) fetch a row's slice of that
+// stripe, and no other XCD does.  Every (stripe, item block) pair is one workgroup by index
+// arithmetic alone; no workgroup waits on another.
+//
+// Same bits as the unstriped kernel: per column the FMAs run in the row's CSR order (one edge
+// group per slot, as there), the epilogue is epi_prefetch / epi_finish at the lane's columns,
+// and a hub row is summed as the 32-lane geometry sums it (hub_sum<VEC, 32>: even chunks in
+// order, odd chunks in order, the two added) — by the wavefront whose chunk slice arrives last
+// of the hub's nch chunks x the stripes inside C (one ticket per hub, counted to their
+// product), over the whole row.
+//
+// Which mapping a launch takes: k1_stripes_for (rhs.hip; GNPDE_K1_STRIPES).
+int k1_stripes_for(int64_t n_items, int64_t C, int stage_kind, int flags);
+void k1_striped_launched();
+
+// A kernel of its own, not a launch-uniform branch of agg_kernel: the branch took the fused-stage
+// instantiation from 60 to 69 VGPRs (8 -> 7 waves per SIMD) on the unstriped path as well.
+//
+// The launches of agg_kernel that agg_stripe_kernel can stand in for.
+template <int VEC, int GL, int NCH, int U, int RPW, int STG, class WP, class T>
+constexpr bool striped_geometry() {
+  return std::is_same<WP, PlainWeights>::value && sizeof(T) == 4 && VEC == 4 && GL == 32 && RPW == 2 && NCH == 1 &&
+         U == 4 && (STG == 0 || STG == 1);
+}
+
+template <int S>
+constexpr int stripe_rpw() {
+  return 2 * S;  // row slots per wavefront: 64 lanes / (32 / S lanes per slot)
+}
+// Workgroups of a striped launch: rounds of 8, each round 8 / S item blocks x S stripes.
+template <int S>
+inline unsigned stripe_grid(int64_t n_items) {
+  const int64_t nib = ceil_div(n_items, (int64_t)kWavesPerBlock * stripe_rpw<S>());
+  return (unsigned)(ceil_div(nib, (int64_t)(kNumXcd / S)) * kNumXcd);
+}
+
+template <int S, int STG>
+__global__ __launch_bounds__(256) void agg_stripe_kernel(const int4* __restrict__ items, int n_items, int4* heavy,
+                                                          int n_heavy, const int* __restrict__ col, PlainWeights wp,
+                                                          int C, Epi ep, float* __restrict__ partials) {
+  static_assert((S == 2 || S == 4) && (STG == 0 || STG == 1), "stripes of the forward epilogues");
+  static_assert(!stage_rowsum<STG, float>(), "no per-row term to reduce across stripes");
+  // U = 8 gathers per batch and the batches of a chunk unrolled (the compiler issues the next
+  // batch's gathers ahead of the wait for this one's): 90-92 VGPRs, 5 waves per SIMD, and the
+  // fastest of the forms measured (U = 4 in a rolled loop, 66 VGPRs and 7 waves,
+  // ran S = 4 10 % behind the unstriped kernel; column ids of 32 edges per round trip, KR = 32 / SL,
+  // came out behind KR = 1 at S = 2).
+  constexpr int VEC = 4, U = 8;
+  constexpr int SL = 32 / S;           // lanes per row slot: one edge group (G = 1)
+  constexpr int KR = 1;                // registers of column ids per lane and chunk
+  constexpr int RPW = stripe_rpw<S>();  // row slots per wavefront
+  constexpr int XS = kNumXcd / S;      // item blocks per round of 8 workgroups
+  const int b = blockIdx.x;
+  const int stripe = (b % kNumXcd) / XS;  // = (b % 8) * S / 8
+  const int ib = (b / kNumXcd) * XS + b % XS;
+  const int c0 = stripe * SL * VEC;
+  if (c0 >= C) return;  // workgroup-uniform: a stripe wholly outside C (S = 4, C <= 96)
+  const int lane = threadIdx.x & 63;
+  const int rs = lane / SL, gl = lane % SL;
+  const int wid = uniform(ib * kWavesPerBlock + (threadIdx.x >> 6));
+  if (wid * RPW >= n_items) return;  // wave-uniform
+  const int item = wid * RPW + rs;
+  const bool live = item < n_items;
+  const int4 it = live ? items[item] : make_int4(0, 0, 0, -1);
+  const int row = it.x, beg = it.y, end = it.z, slot = it.w;
+  const int cc = c0 + gl * VEC;
+  const bool inc = cc < C;  // a last stripe partly inside C
+  const bool owner = live && slot < 0 && inc;
+
+  EpiPre<VEC, float, STG> pre;
+  if (owner) epi_prefetch<VEC, STG, float>(ep, row, cc, pre);  // ahead of the aggregation
+  float acc[VEC];
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) acc[t] = 0.f;
+  const float* __restrict__ xb = ep.x + cc;
+  // A slot takes the column ids and weights of CH = KR * SL edges in one round trip (KR
+  // registers per lane), then gathers them U at a time, in CSR order.
+  constexpr int CH = KR * SL;
+  for (int e0 = beg; e0 < end; e0 += CH) {
+    const int n = min(CH, end - e0);
+    int mc[KR];
+    float mw[KR];
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+      const int e = k * SL + gl;
+      mc[k] = 0;
+      mw[k] = 0.f;
+      if (e < n) {
+        mc[k] = col[e0 + e];
+        mw[k] = wp.w[e0 + e];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+      const int nk = min(SL, n - k * SL);  // the slot's edges in register k (the lanes of a slot agree)
+#pragma unroll
+      for (int j = 0; j < SL; j += U) {
+        if (j >= nk) break;
+        Packed<VEC, float> v[U];
+        float ww[U];
+        int srcl[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int jj = j + u;
+          const int src = rs * SL + (jj < nk ? jj : 0);
+          srcl[u] = src;
+          const int c = __shfl(mc[k], src);
+          if (jj < nk && inc) {
+            load_packed<VEC>(xb + (int64_t)c * ep.ldx, v[u]);
+          } else {
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) v[u].d[t] = 0u;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const float wsl = __shfl(mw[k], srcl[u]);
+          ww[u] = j + u < nk ? wsl : 0.f;
+        }
+        // the edges of a row in CSR order (an edge that is not there adds 0 * 0: acc is never -0)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int t = 0; t < VEC; ++t) acc[t] = fmaf(ww[u], unpack(v[u], t), acc[t]);
+      }
+    }
+  }
+
+  const bool chunk = live && slot >= 0;
+  const bool anyc = n_heavy > 0 && __ballot(chunk) != 0;  // wave-uniform
+  if (anyc && chunk) {  // this stripe's slice of the chunk's partial, write-through
+    const __amdgpu_buffer_rsrc_t rp = buf_rsrc(partials);
+    buf_store_wt<VEC>(rp, inc ? (uint32_t)(((int64_t)slot * C + cc) * 4) : kBufNone, acc);
+  }
+  const float a = (ep.flags & GNPDE_EPI_RHS) ? epi_alpha(ep) : 1.f;
+  const float bt = (ep.flags & GNPDE_ADD_SOURCE) ? *ep.beta : 0.f;
+  // The whole rows first: their operands and sums are dead before a hub's epilogue begins.
+  if (owner) epi_finish<VEC, STG, float>(ep, row, cc, acc, a, bt, pre, nullptr);
+  if (!anyc) return;
+
+  // Hub chunks (hub_claim's protocol): the partial slices drained, one arrival per chunk slot
+  // and stripe on the hub's ticket; the arrival that completes nch x (stripes inside C) has the
+  // whole row summed and finished by this wavefront, 32 lanes over the columns as the unstriped
+  // geometry's hub_sum, and resets the ticket for the next launch on this plan.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const int nstr = (C + SL * VEC - 1) / (SL * VEC);
+  int lo = 0, won = 0;
+  if (chunk) {
+    int hi = n_heavy - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (heavy[mid].y <= slot)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    if (gl == 0) {
+      const int t = __hip_atomic_fetch_add(&heavy[lo].w, 1, kHubTicketOrder, __HIP_MEMORY_SCOPE_AGENT);
+      won = t == heavy[lo].z * nstr - 1;
+    }
+  }
+#pragma unroll 1
+  for (int s = 0; s < RPW; ++s) {
+    if (__shfl(won, s * SL)) {  // wave-uniform
+      const int h = __shfl(lo, s * SL);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      const int4 hv = heavy[h];
+      float hs[1][VEC];
+      hub_sum<VEC, 32, 1>(uniform(hv.y), uniform(hv.z), C, partials, hs);
+      // both 32-lane groups hold the row's sums; the first one stores
+      if (lane < 32 && lane * VEC < C) epilogue_store<VEC, STG, float>(ep, uniform(hv.x), lane * VEC, hs[0], a, bt);
+      if (lane == 0) __hip_atomic_store(&heavy[h].w, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ aggregation kernel
 // Lane layout: RPW row slots of SL = 64/RPW lanes per wavefront (one plan item
 // each); inside a slot lane = g*GL + gl: G = SL/GL edges are gathered side by
@@ -845,15 +1028,35 @@ static int launch_agg_cfg(const int4* items, int64_t n_items, int4* heavy, int64
     } else if (stg == 3)
       agg_kernel<VEC, GL, NCH, U, RPW, 3, PlainWeights, float><<<grid, kBlock, 0, s>>>(
           items, (int)n_items, heavy, nh, col, as_plain(wp), C, ep, partials);
-    else if (stg == 1)
-      agg_kernel<VEC, GL, NCH, U, RPW, 1, WP, T><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, wp, C, ep,
-                                                                          partials);
     else if (stg == 2)
       agg_kernel<VEC, GL, NCH, U, RPW, 2, WP, T><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, wp, C, ep,
                                                                           partials);
-    else
-      agg_kernel<VEC, GL, NCH, U, RPW, 0, WP, T><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, wp, C, ep,
-                                                                          partials);
+    else {
+      // stage kinds 0 and 1; the headline geometry on a large graph in column stripes (agg_stripe_kernel)
+      int stripes = 0;
+      if constexpr (striped_geometry<VEC, GL, NCH, U, RPW, 0, WP, T>()) stripes = k1_stripes_for(n_items, C, stg, ep.flags);
+      if (stripes) {
+        if constexpr (striped_geometry<VEC, GL, NCH, U, RPW, 0, WP, T>()) {
+#define GNPDE_STRIPED(S, STG)                                                                                       \
+  agg_stripe_kernel<S, STG><<<stripe_grid<S>(n_items), kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, wp, C, ep, \
+                                                                        partials)
+          if (stripes == 4) {
+            if (stg == 1) GNPDE_STRIPED(4, 1);
+            else GNPDE_STRIPED(4, 0);
+          } else {
+            if (stg == 1) GNPDE_STRIPED(2, 1);
+            else GNPDE_STRIPED(2, 0);
+          }
+#undef GNPDE_STRIPED
+          k1_striped_launched();
+        }
+      } else if (stg == 1)
+        agg_kernel<VEC, GL, NCH, U, RPW, 1, WP, T><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, wp, C,
+                                                                            ep, partials);
+      else
+        agg_kernel<VEC, GL, NCH, U, RPW, 0, WP, T><<<grid, kBlock, 0, s>>>(items, (int)n_items, heavy, nh, col, wp, C,
+                                                                            ep, partials);
+    }
     GNPDE_LAUNCH_CHECK();
   }
   return GNPDE_OK;

@@ -4,9 +4,67 @@
 #include "aggregate.hpp"
 #include "rhs_host.hpp"
 
+#include <atomic>
+#include <cstdlib>
+
 using namespace gnpde;
 
+// ------------------------------------------------------------------ column stripes: which launches
+// 0, 2, 4: no stripes, S = 2, S = 4 for every launch of the headline geometry, whatever its size
+// (A/B runs and the tests); otherwise by the shape (below).  GNPDE_K1_STRIPES is read once;
+// gnpde_k1_stripes_set overrides it, or (-1) gives the decision back to it.
+namespace {
+std::atomic<int> g_stripes_set{-1};  // -1: not set through the ABI
+std::atomic<long long> g_striped_launches{0};
+
+int stripes_env() {
+  static const int v = [] {
+    const char* e = std::getenv("GNPDE_K1_STRIPES");
+    if (!e || !*e) return -1;
+    const int s = std::atoi(e);
+    return (s == 0 || s == 2 || s == 4) ? s : -1;
+  }();
+  return v;
+}
+}  // namespace
+
+namespace gnpde {
+// Unforced, only the fused-stage launch (stage kind 1) of a large graph is striped, with S = 2:
+// that is what was measured to win.  The bar is the measured crossover of that
+// launch on RMAT graphs of the headline's density at C = 128: 49,152 rows lose (103 against 75 us;
+// such graphs are planned in 16-edge chunks, whose many chunk slices the stripes multiply),
+// 65,536 rows win (52 against 56 us), 98,304 win by 18 %; S = 4 loses or ties at every size.  The
+// items of a launch stand for its rows.  The plain launch (stage kind 0) was not measured apart
+// from the headline solve and stays unstriped.  And only launches that carry GNPDE_LIVE_ITEMS — the
+// no-grad rk4 solve in the node layout's numbering with its frozen rows left out, which gains
+// 13 % per launch — are striped: the same stage launches in the caller's numbering tie at best,
+// and the dopri5, training and hard-attention legs of the bench lost 3 - 10 % with them striped.
+constexpr int kStripesDefault = 2;
+constexpr int64_t kStripeMinTableBytes = (int64_t)65536 * 128 * sizeof(float);
+
+int k1_stripes_for(int64_t n_items, int64_t C, int stage_kind, int flags) {
+  const int set = g_stripes_set.load(std::memory_order_relaxed);
+  const int mode = set >= 0 ? set : stripes_env();
+  if (mode >= 0) return mode;
+  return stage_kind == 1 && (flags & GNPDE_LIVE_ITEMS) && n_items * C * (int64_t)sizeof(float) >= kStripeMinTableBytes ? kStripesDefault : 0;
+}
+void k1_striped_launched() { g_striped_launches.fetch_add(1, std::memory_order_relaxed); }
+}  // namespace gnpde
+
 extern "C" {
+
+int gnpde_k1_stripes_set(int stripes) {
+  GNPDE_REQUIRE(stripes == -1 || stripes == 0 || stripes == 2 || stripes == 4, GNPDE_EINVAL,
+                "k1_stripes_set: stripes=%d not in {-1, 0, 2, 4}", stripes);
+  g_stripes_set.store(stripes, std::memory_order_relaxed);
+  return GNPDE_OK;
+}
+
+int gnpde_k1_stripes_for(int64_t n_items, int64_t C, int stage_kind, int flags) {
+  return k1_stripes_for(n_items, C, stage_kind, flags);
+}
+
+int64_t gnpde_k1_striped_launches(void) { return (int64_t)g_striped_launches.load(std::memory_order_relaxed); }
 
 int gnpde_spmm_rhs_f32(const int32_t* items, int64_t n_items, int32_t* heavy, int64_t n_heavy,
                        const int32_t* col, const float* w, int64_t C, const float* x, int64_t ldx, const float* x0,

@@ -71,6 +71,9 @@ SIGNATURES = {
                                   _i64, _vp, _i64, ctypes.POINTER(StageEpilogue), _vp]),
     "gnpde_spmm_rhs_frozen_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _int, _i64, _vp, _i64,
                                          ctypes.POINTER(StageEpilogue), _vp, _i64, _i64, _i64, _vp]),
+    "gnpde_k1_stripes_set": (_int, [_int]),
+    "gnpde_k1_stripes_for": (_int, [_i64, _i64, _int, _int]),
+    "gnpde_k1_striped_launches": (_i64, []),
     "gnpde_spmm_rhs_bf16": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp,
                                    _i64, _vp, _i64, ctypes.POINTER(StageEpilogue), _vp]),
     "gnpde_attn_ref_rhs_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64,
@@ -197,6 +200,7 @@ EPI_PLAIN = 0
 EPI_RHS = 1
 ALPHA_SIGMOID = 2
 ADD_SOURCE = 4
+LIVE_ITEMS = 8  # a hint: the live items of a node layout's graph (the frozen rows left out)
 SCORE_REFERENCE = 0
 SCORE_DOT = 1
 SCORE_EXP_KERNEL = 2

@@ -912,8 +912,10 @@ def spmm_rhs(g, w_csr, x, x0=None, alpha=None, beta=None, rhs=True, alpha_sigmoi
                 or add_source or not rhs):
             raise ValueError("spmm_rhs: frozen rows take the plain-weight fp32 stage launches of their own graph")
         if home is None:
+            # GNPDE_LIVE_ITEMS: the launch code stripes these launches' columns on a large graph
+            live = epi[:7] + (epi[7] | _lib.LIVE_ITEMS,) + epi[8:]
             _lib.call("gnpde_spmm_rhs_f32", _ptr(items), fr.n_live_items, _ptr(plan.heavy), plan.n_heavy,
-                      _ptr(col), _ptr(w_csr), *epi)
+                      _ptr(col), _ptr(w_csr), *live)
         else:
             hr = _rows(home, "frozen home", dt)
             if hr.shape != xr.shape:

@@ -57,6 +57,9 @@ extern "C" {
 #define GNPDE_EPI_RHS 1            /* f = a*(ax - x) [+ b*x0]                  */
 #define GNPDE_ALPHA_SIGMOID 2      /* a = sigmoid(*alpha) instead of *alpha    */
 #define GNPDE_ADD_SOURCE 4         /* add b*x0 (b = *beta)                      */
+#define GNPDE_LIVE_ITEMS 8         /* a hint, no arithmetic: the launch runs the live items of a graph in the node
+                                      layout's numbering (rows by in-degree, the frozen rows of an rk4 solve left
+                                      out): the launches measured to gain from column stripes */
 
 /* score modes of the attention RHS (function_transformer_attention.py:246-259) */
 #define GNPDE_SCORE_REFERENCE 0    /* fork scaled_dot: q_src . (sum_e' k_dst(e')) / sqrt(dk)      */
@@ -375,6 +378,26 @@ int gnpde_spmm_rhs_frozen_f32(const int32_t* items, int64_t n_live_items, int32_
                               const float* alpha, int flags, int64_t ldf, float* partials, int64_t n_slots,
                               const gnpde_stage_epilogue_t* stage, const float* home, int64_t row0, int64_t row1,
                               int64_t steps, void* stream);
+
+/* Column stripes of K1's headline geometry (fp32 rows of 65-128 columns in 16-byte
+ * slices, plain weights, stage kinds 0 and 1: store f, or one fixed-grid stage
+ * output).  On a graph whose gathered rows overflow one XCD's L2, gnpde_spmm_rhs_f32
+ * has each workgroup aggregate 128 / S columns of all its rows (S = 4 or 2) and
+ * deals the stripes to the XCDs, so that a row slice is fetched by 8 / S of the
+ * eight L2s instead of nearly all of them.  The bits are those of the unstriped
+ * launch.  The environment variable GNPDE_K1_STRIPES = 0 | 2 | 4 (read once)
+ * selects no stripes, S = 2 or S = 4 for EVERY launch of that geometry, whatever its
+ * size; unset, the launch code decides from the shape: S = 2 for the stage launches
+ * (one fixed-grid stage output) of at least 65,536 rows x 128 columns of state that
+ * carry GNPDE_LIVE_ITEMS, no stripes otherwise.  gnpde_k1_stripes_set
+ * overrides the variable: 0, 2, 4 as above; -1 removes the override.
+ * gnpde_k1_stripes_for: the stripe count (0, 2, 4) a launch of n_items items of C
+ * columns, stage kind 0 (store f) or 1 (a stage output) and flags `flags` in that
+ * geometry takes under the current setting.
+ * gnpde_k1_striped_launches: striped launches issued by this process so far.    */
+int gnpde_k1_stripes_set(int stripes);
+int gnpde_k1_stripes_for(int64_t n_items, int64_t C, int stage_kind, int flags);
+int64_t gnpde_k1_striped_launches(void);
 
 /* K1 on bfloat16 storage (configs[3], BLEND in bf16): x, x0, f and every
  * stage pointer of `stage` address bf16 arrays (raw uint16 bits; the stage

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Per-stage times of the headline K1 in a rocprofv3 kernel trace of
 `bench.py --gpus 1 --steps K --warmup W`: the last 4 K dispatches of the fused-stage
-kernel (and of its frozen-tail form, a step's last launch) are the timed solve's, four
+kernel (of its column-striped form, and of its frozen-tail form, the solve's last launch) are the
+timed solve's, four
 per rk4 step in stage order.
 python tools/k1_stage_times.py <run_kernel_trace.csv> [K]"""
 import csv
@@ -11,12 +12,15 @@ import sys
 NAME = "void gnpde::agg_kernel<4, 32, 1, 4, 2, 1, gnpde::PlainWeights, float>"
 # a step's last launch on a graph with frozen rows (kStgFrozen)
 NAME_FROZEN = "void gnpde::agg_kernel<4, 32, 1, 4, 2, 6, gnpde::PlainWeights, float>"
+# the same stage launch in S column stripes (large graphs)
+NAMES_STRIPED = ("void gnpde::agg_stripe_kernel<4, 1>", "void gnpde::agg_stripe_kernel<2, 1>")
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows
-            if r["Kernel_Name"].startswith((NAME, NAME_FROZEN)))
-print("K1 fused-stage dispatches: %d | name: %s" % (len(ev), NAME))
+            if r["Kernel_Name"].startswith((NAME, NAME_FROZEN) + NAMES_STRIPED))
+striped = sum(r["Kernel_Name"].startswith(NAMES_STRIPED) for r in rows)
+print("K1 fused-stage dispatches: %d (%d striped) | names: %s*, %s*" % (len(ev), striped, NAME, NAMES_STRIPED[0][:-5]))
 ev = ev[-4 * steps:]
 for s in range(4):
     d = [(e - b) / 1e3 for b, e in ev[s::4]]
