@@ -19,7 +19,7 @@ from .function_transformer_attention import ODEFuncTransformerAtt, SpGraphTransA
 from .model_configurations import set_block, set_function  # noqa: F401
 from .integrator import odeint  # noqa: F401
 from .early_stop_solver import EarlyStopInt  # noqa: F401
-from .graph_rewiring import KNN, apply_KNN  # noqa: F401
+from .graph_rewiring import KNN, apply_KNN, GDCWrapper, apply_gdc  # noqa: F401
 from .utils import MaxNFEException  # noqa: F401
 
 __version__ = "0.1.0"

@@ -188,6 +188,8 @@ SIGNATURES = {
     "gnpde_two_hop_bound_i32": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "gnpde_two_hop_count_i32": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "gnpde_two_hop_fill_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "gnpde_topk_cols_workspace_bytes": (_size, [_i64, _i64, _i64, _i64]),
+    "gnpde_topk_cols_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _size, _vp]),
 }
 
 # constants mirrored from include/gnpde.h

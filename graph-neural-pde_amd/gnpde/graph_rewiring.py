@@ -1,4 +1,6 @@
-"""kNN graph rewiring (the reference's ``rewire_KNN``; src/graph_rewiring.py:122-161, called
+"""Graph rewiring: kNN and GDC.
+
+kNN graph rewiring (the reference's ``rewire_KNN``; src/graph_rewiring.py:122-161, called
 from the training loop at src/graph_datasets/run_GNN.py:252-254): every
 ``rewire_KNN_epoch`` epochs the graph becomes the k nearest neighbours of the current node
 embeddings.  The reference delegates the search to ``pykeops.LazyTensor.argKmin``; here it
@@ -30,6 +32,43 @@ The reference's lines read as they are meant:
 * Errors.  k above the number of unmasked rows of any batch element raises ValueError;
   this is the one host read per rewire (the per-graph counts of the mask pre-pass).  A
   bf16 or CPU ``x`` raises, as elsewhere on the product path.
+
+GDC graph diffusion rewiring (the reference's ``--rewiring gdc`` and BLEND's
+``pos_enc_type='GDC'``: ``apply_gdc`` src/graph_rewiring.py:42-81, ``GDCWrapper`` :378-434,
+which subclass PyG's ``GDC``).  PyG is not a dependency: what follows is a definition, not a
+parity claim against PyG's tie behaviour or its push approximation.  One graph (B = 1; B > 1
+raises NotImplementedError): ``edge_index`` [2, E] or [1, 2, E] int64, optional weights
+``edge_attr`` (ones otherwise), N = ``num_nodes``.
+
+1. Self loops.  ``__call__``: M = coalesce(A) + w_self I, duplicates summed, w_self =
+   ``self_loop_weight`` (0 / None: none) — PyG's add_self_loops then coalesce.
+   ``position_encoding``: add_remaining_self_loops (:407-410) — an existing loop keeps its
+   weight, a missing one gets w_self (``ops.add_self_loops``).
+2. ``normalization_in='sym'``: T = D^-1/2 M D^-1/2, deg the column sums, inf -> 0
+   (``ops.norm_weights``, GCN).  DEPARTURE: M must be symmetric; it is checked once on the
+   device and a non-symmetric input raises ValueError (symmetrise with ``to_undirected``).
+   The reference's datasets are undirected, and the iteration bounds rest on T's spectrum
+   lying in [-1, 1].
+3. Diffusion.  'ppr': S = alpha (I - (1 - alpha) T)^-1; any other ``gdc_method``: heat,
+   S = exp(-t (I - T)).  Column blocks of up to 128 seeds, each a short polynomial
+   recurrence in T on the SpMM kernel (``ops.diffusion_schedule`` / ``ops.diffusion_block``:
+   Chebyshev iteration for ppr, Horner on the Taylor series for heat), truncated at
+   tol = 1e-6 of the column's scale.
+4. Sparsification.  'topk' (dim = 0): per column j the k entries S[i, j] largest in the total
+   order (value descending, i ascending) as edges (i, j); zeros are candidates like any
+   value, so a component smaller than k pads with zero-weight edges to the lowest indices
+   and E = N k always; k > N raises ValueError.  'threshold': the entries with
+   S[i, j] >= ``gdc_threshold``.
+5. ``normalization_out='col'``: every kept weight divided by its column's kept sum (topk:
+   the sum in rank order, sequentially in fp32: the bits do not depend on the tiling).
+6. ``type='combined'``: the edges sorted by (row, col) with their weights, written into
+   ``data.edge_index`` / ``data.edge_attr`` at the rank they came in.
+7. ``type='pos_encoding'``: the dense [N, N] column-normalised S without sparsification
+   (:419-434), transposed for ``pos_enc_orientation='col'``; N N 4 bytes above ``max_bytes``
+   (8 GiB) raises ValueError.
+8. ``exact``.  DEPARTURE: both settings return the exact matrix to the tolerance above (the
+   push approximation's own error is not reproduced).  ``exact=False`` with a self-loop
+   weight other than 1 raises ValueError (the wrapper's assert).
 """
 import torch
 
@@ -79,3 +118,106 @@ def apply_KNN(x, graph_data, x2, pos_encoding, model, opt):
     else:
         raise Exception("Need to set rewire_KNN_T")
     return ei
+
+
+class GDCWrapper(object):
+    """The reference's GDCWrapper (src/graph_rewiring.py:378-434) without a PyG base class:
+    ``__call__(data)`` rewires ``data`` (any object with edge_index, edge_attr, num_nodes),
+    ``position_encoding(data)`` returns the dense column-normalised diffusion matrix.
+    gdc: the driver, ``ops.gdc`` by default; ``ops.gdc_torch`` is the same contract in torch
+    ops on any device.
+    The constructor's defaults are the reference's, and its default ``sparsification_kwargs``
+    (threshold by ``avg_degree``) is NOT served: ``__call__`` takes ``method='topk'`` with ``k``
+    (``dim`` 0) or ``method='threshold'`` with ``eps`` and raises NotImplementedError for
+    anything else, so a default-constructed wrapper serves ``position_encoding`` only (which
+    does not sparsify).  ``apply_gdc`` always passes one of the two served forms."""
+
+    def __init__(self, self_loop_weight=1, normalization_in='sym', normalization_out='col',
+                 diffusion_kwargs=dict(method='ppr', alpha=0.15),
+                 sparsification_kwargs=dict(method='threshold', avg_degree=64), exact=True, gdc=None,
+                 max_bytes=ops.GDC_MAX_BYTES):
+        if normalization_in != 'sym' or normalization_out != 'col':
+            raise NotImplementedError("GDCWrapper: normalization_in='sym' and normalization_out='col' (the "
+                                      "reference's apply_gdc) are the supported normalisations")
+        self.self_loop_weight = self_loop_weight
+        self.normalization_in = normalization_in
+        self.normalization_out = normalization_out
+        self.diffusion_kwargs = dict(diffusion_kwargs)
+        self.sparsification_kwargs = dict(sparsification_kwargs)
+        self.exact = exact
+        self.gdc = gdc
+        self.max_bytes = max_bytes
+        if self_loop_weight and not (exact or self_loop_weight == 1):
+            raise ValueError("GDCWrapper: exact=False needs self_loop_weight == 1, got %r" % (self_loop_weight,))
+
+    def _args(self, dense):
+        d, s = self.diffusion_kwargs, self.sparsification_kwargs
+        kw = dict(method='ppr' if d.get('method') == 'ppr' else 'heat', self_loop_weight=self.self_loop_weight or 0.0,
+                  dense=dense, max_bytes=self.max_bytes)
+        if kw['method'] == 'ppr':
+            kw['alpha'] = d['alpha']
+        else:
+            kw['t'] = d['t']
+        if not dense:
+            if s.get('method') == 'topk':
+                if s.get('dim', 0) != 0:
+                    raise NotImplementedError("GDCWrapper: topk with dim=0 (per column) only")
+                kw.update(sparsification='topk', k=int(s['k']))
+            elif s.get('method') == 'threshold' and 'eps' in s:
+                kw.update(sparsification='threshold', threshold=float(s['eps']))
+            else:
+                raise NotImplementedError("GDCWrapper: sparsification %r (topk with k | threshold with eps)" % (s,))
+        return kw
+
+    def _run(self, data, dense):
+        ei = data.edge_index
+        batched = ei.dim() == 3
+        if batched and ei.shape[0] != 1:
+            raise NotImplementedError("gnpde: GDC with B > 1: the rewired edge count differs per graph")
+        w = data.edge_attr
+        if w is not None:
+            w = w.reshape(-1)
+        N = data.num_nodes[0] if isinstance(data.num_nodes, list) else data.num_nodes
+        with torch.no_grad():
+            out = (ops.gdc if self.gdc is None else self.gdc)(ei, w, int(N), **self._args(dense))
+        return out, batched
+
+    def __call__(self, data):
+        (ei, w), batched = self._run(data, False)
+        data.edge_index = ei.unsqueeze(0) if batched else ei
+        data.edge_attr = w.unsqueeze(0) if batched else w
+        return data
+
+    def position_encoding(self, data):
+        return self._run(data, True)[0]
+
+
+def apply_gdc(data, opt, type="combined", gdc=None):
+    """The reference's apply_gdc (src/graph_rewiring.py:42-81) with its option mapping:
+    gdc_method ('ppr', anything else: heat), ppr_alpha / heat_time, gdc_sparsification ('topk':
+    gdc_k per column; otherwise the threshold gdc_threshold), self_loop_weight (0: no self
+    loops), exact; type 'combined' rewires ``data``, 'pos_encoding' returns the dense encoding
+    (pos_enc_orientation 'row', or 'col': its transpose)."""
+    if opt['gdc_method'] == 'ppr':
+        diff_args = dict(method='ppr', alpha=opt['ppr_alpha'])
+    else:
+        diff_args = dict(method='heat', t=opt['heat_time'])
+    if opt['gdc_sparsification'] == 'topk':
+        sparse_args = dict(method='topk', k=opt['gdc_k'], dim=0)
+    else:
+        sparse_args = dict(method='threshold', eps=opt['gdc_threshold'])
+    diff_args['eps'] = opt['gdc_threshold']
+    slw = float(opt['self_loop_weight']) if opt['self_loop_weight'] != 0 else None
+    wrapper = GDCWrapper(slw, normalization_in='sym', normalization_out='col', diffusion_kwargs=diff_args,
+                         sparsification_kwargs=sparse_args, exact=opt['exact'], gdc=gdc)
+    if isinstance(data.num_nodes, list):
+        data.num_nodes = data.num_nodes[0]
+    if type == 'combined':
+        return wrapper(data)
+    if type == 'pos_encoding':
+        if opt['pos_enc_orientation'] == "row":
+            return wrapper.position_encoding(data)
+        if opt['pos_enc_orientation'] == "col":
+            return wrapper.position_encoding(data).T
+        raise ValueError("apply_gdc: pos_enc_orientation %r (row | col)" % (opt['pos_enc_orientation'],))
+    return data

@@ -10,6 +10,7 @@ Layout: node features [B,N,C] fp32 row-major, viewed as
 (rowptr[R+1], col[nnz] global node ids, perm[nnz] CSR pos -> COO edge id).
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -2718,3 +2719,403 @@ def two_hop(g_or_csr, w, num_nodes=None, lds_max=None, scratch_bytes=None, retur
               _ptr(bits), _ptr(out_ptr), nnz, _ptr(out_col), _ptr(out_val), _ptr(out_ei), st)
     out = (out_ei, out_val[:nnz], out_ptr)
     return out + (out_col[:nnz],) if return_col else out
+
+
+# --------------------------------------------------------------------------- GDC diffusion rewiring
+TOPK_COLS_MAX_K = 128          # the kernel's range (csrc/topk_cols.hip kTkMaxK)
+GDC_BLOCK = 128                # seeds of one column block: K1's headline width
+GDC_MAX_BYTES = 8 << 30        # the dense positional encoding's size guard
+# The seed term of a diffusion launch (diffusion_block): from this many rows on it is added to
+# the block's diagonal after the launch instead of streaming E_J as a stage operand.  Measured
+# at two sizes only (profiles/gdc_bench.json): 169,343 rows 99.8 against 111.9 us per product;
+# 2,708 rows, where the extra launch is what costs, 26.2 against 21.9.  The crossover between
+# them is not measured: the limit is LAYOUT_MIN_ROWS, below which the state sits in cache.
+GDC_DIAGONAL_MIN_ROWS = 32768
+
+
+def _topk_cols_input(y, k, ncols, name):
+    if not isinstance(y, torch.Tensor):
+        raise TypeError("%s: y must be a torch.Tensor" % name)
+    if y.dtype != torch.float32:
+        raise TypeError("gnpde: %s: y must be torch.float32, got %s" % (name, y.dtype))
+    if y.dim() != 2:
+        raise ValueError("%s: y must be [N, ld], got %s" % (name, tuple(y.shape)))
+    N, ld = y.shape
+    ncols = ld if ncols is None else int(ncols)
+    k = int(k)
+    if not 0 <= ncols <= ld:
+        raise ValueError("%s: ncols=%d must be in [0, ld=%d]" % (name, ncols, ld))
+    if k < 1:
+        raise ValueError("%s: k=%d must be >= 1" % (name, k))
+    if k > N:
+        raise ValueError("%s: k=%d exceeds the %d rows of the block" % (name, k, N))
+    return N, ld, ncols, k
+
+
+def _value_order_code(v):
+    """int64 code of fp32 values whose ascending order is the values' DESCENDING order
+    (-0 as +0): csrc/topk_cols.hip tk_encode, shifted into the signed range."""
+    u = v.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    u = torch.where((u & 0x7FFFFFFF) == 0, torch.zeros_like(u), u)
+    m = torch.where(u >= 0x80000000, 0xFFFFFFFF - u, u + 0x80000000)
+    return (0xFFFFFFFF - m) - 0x80000000
+
+
+def rank_order_sum(val):
+    """val [n, k] fp32 -> the sum of every row taken sequentially in fp32, column 0 first."""
+    s = torch.zeros(val.shape[0], dtype=torch.float32, device=val.device)
+    for i in range(val.shape[1]):
+        s = s + val[:, i]
+    return s
+
+
+def topk_cols_torch(y, k, ncols=None):
+    """gnpde_topk_cols_f32 restated in torch ops (any device): for every column c < ncols of
+    the row-major block y [N, ld] the k entries largest in the total order (value descending,
+    row ascending; -0 as +0) -> (idx int32 [ncols, k], val fp32 [ncols, k], wnorm fp32
+    [ncols, k]), wnorm = val / the sequential fp32 sum of val in rank order (0 for a zero sum).
+    One integer key per entry, so the result does not depend on topk's tie behaviour."""
+    N, ld, ncols, k = _topk_cols_input(y, k, ncols, "topk_cols_torch")
+    dev = y.device
+    yt = y[:, :ncols].t().contiguous()                                        # [ncols, N]
+    key = (_value_order_code(yt) << 32) + torch.arange(N, dtype=torch.int64, device=dev)
+    top = torch.topk(key, k, dim=1, largest=False, sorted=True).values
+    idx = top & 0xFFFFFFFF
+    val = torch.gather(yt, 1, idx)
+    val = torch.where(val == 0, torch.zeros_like(val), val)
+    s = rank_order_sum(val).unsqueeze(1)
+    wnorm = torch.where(s == 0, torch.zeros_like(val), val / s)
+    return idx.to(torch.int32), val, wnorm
+
+
+def topk_cols(y, k, ncols=None, rows_per_wg=None):
+    """gnpde_topk_cols_f32 (csrc/topk_cols.hip): the k largest entries of every column
+    c < ncols (default: all) of the contiguous row-major block y [N, ld] fp32, in the total
+    order (value descending, row ascending) -> (idx int32 [ncols, k], val, wnorm) as
+    topk_cols_torch.  Finite inputs; 1 <= k <= 128 and k <= N.  rows_per_wg (tests only): the
+    rows one workgroup scans; the outputs do not depend on it."""
+    N, ld, ncols, k = _topk_cols_input(y, k, ncols, "topk_cols")
+    _require_gpu(y, "y", torch.float32)
+    if not y.is_contiguous():
+        raise ValueError("topk_cols: y must be contiguous")
+    dev = y.device
+    rp = 0 if rows_per_wg is None else int(rows_per_wg)
+    idx = torch.empty(ncols, k, dtype=torch.int32, device=dev)
+    val = torch.empty(ncols, k, dtype=torch.float32, device=dev)
+    wnorm = torch.empty(ncols, k, dtype=torch.float32, device=dev)
+    nbytes = int(_lib.fn("gnpde_topk_cols_workspace_bytes")(N, ncols, k, rp))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.call("gnpde_topk_cols_f32", _ptr(y), N, ncols, ld, k, _ptr(idx), _ptr(val), _ptr(wnorm), rp, _ptr(ws),
+              nbytes, _stream(dev))
+    return idx, val, wnorm
+
+
+class DiffusionSchedule(object):
+    """The coefficient schedule of one diffusion column block (diffusion_schedule): the
+    iterate starts at ``init`` * E_J and every step forms, with one product T·x,
+        x_next = cb * x_prev + cf * (T x) + ce * E_J      (steps: [(cb, cf, ce), ...]),
+    x_prev the iterate before x (``two_term``; absent, i.e. 0, at the first step) — or no
+    such term at all.  ``bound``: the 2-norm distance of the last iterate from the exact
+    column in exact arithmetic."""
+
+    def __init__(self, method, param, init, steps, two_term, bound):
+        self.method, self.param, self.init, self.steps = method, param, init, steps
+        self.two_term, self.bound = two_term, bound
+
+    @property
+    def products(self):
+        return len(self.steps)
+
+
+def diffusion_schedule(method, alpha=None, t=None, tol=1e-6):
+    """Host code only.  'ppr': the Chebyshev iteration on (I - (1 - alpha) T) s = alpha e for
+    a spectrum in [alpha, 2 - alpha] (T symmetric with its spectrum in [-1, 1]):
+    x_0 = 0, x_1 = alpha E, x_{m+1} = w_{m+1} (1 - alpha) T x_m + (1 - w_{m+1}) x_{m-1} +
+    w_{m+1} alpha E with w_2 = 1 / (1 - q/2), w_{m+1} = 1 / (1 - w_m q / 4), q = (1 - alpha)^2,
+    stopped at the first m with 2 rho^m <= tol alpha, rho = (sqrt(kappa) - 1) / (sqrt(kappa) +
+    1), kappa = (2 - alpha) / alpha (|x_m - s|_2 <= 2 rho^m |s|_2 and |S e_j|_2 <= 1).
+    'heat': Horner on the Taylor series theta_p = e^-t t^p / p!: Y = theta_K E, then
+    Y <- T Y + theta_p E for p = K - 1 .. 0, K the first index whose tail sum_{p > K} theta_p
+    is at most tol e^-t."""
+    tol = float(tol)
+    if not tol > 0:
+        raise ValueError("diffusion_schedule: tol=%r must be positive" % tol)
+    if method == 'ppr':
+        a = float(alpha)
+        if not 0.0 < a < 1.0:
+            raise ValueError("diffusion_schedule: ppr alpha=%r must be in (0, 1)" % a)
+        kappa = (2.0 - a) / a
+        rho = (math.sqrt(kappa) - 1.0) / (math.sqrt(kappa) + 1.0)
+        m = 1
+        while 2.0 * rho ** m > tol * a:
+            m += 1
+        q = (1.0 - a) ** 2
+        steps, w = [], None
+        for _ in range(m - 1):  # x_2 .. x_m
+            w = 1.0 / (1.0 - q / 2.0) if w is None else 1.0 / (1.0 - w * q / 4.0)
+            steps.append((1.0 - w, w * (1.0 - a), w * a))
+        return DiffusionSchedule('ppr', a, a, steps, True, 2.0 * rho ** m)
+    if method == 'heat':
+        tt = float(t)
+        if not tt >= 0.0:
+            raise ValueError("diffusion_schedule: heat t=%r must be >= 0" % tt)
+        e = math.exp(-tt)
+        theta, total = [e], e
+        while 1.0 - total > tol * e and len(theta) < 1000:
+            theta.append(theta[-1] * tt / len(theta))
+            total += theta[-1]
+        K = len(theta) - 1
+        steps = [(0.0, 1.0, theta[p]) for p in range(K - 1, -1, -1)]
+        return DiffusionSchedule('heat', tt, theta[K], steps, False, max(1.0 - total, 0.0))
+    raise ValueError("diffusion_schedule: method %r (ppr | heat)" % (method,))
+
+
+def _seed_block(N, j0, ncols, device, dtype=torch.float32):
+    """E_J [N, ncols]: column c is the unit vector of node j0 + c."""
+    E = torch.zeros(N, ncols, dtype=dtype, device=device)
+    E[j0:j0 + ncols].fill_diagonal_(1.0)
+    return E
+
+
+def diffusion_block(g, w, j0, ncols, schedule, seed=None):
+    """The columns [j0, j0 + ncols) of the diffusion matrix of T (GraphCSR ``g`` with
+    CSR-order weights ``w``, symmetric) by ``schedule``: one K1 launch per product, the
+    step's combination fused into its stage epilogue, two [N, ncols] buffers in turn (the
+    ppr output overwrites x_{m-1}, its own base).  seed: 'operand' — E_J materialised once and
+    passed as the stage's operand; 'diagonal' — no operand, ce added to the block's diagonal
+    after the launch; None — by size (GDC_DIAGONAL_MIN_ROWS).  -> fp32 [N, ncols]."""
+    if g.B != 1:
+        raise NotImplementedError("gnpde: diffusion_block: only B = 1 is supported")
+    if seed is None:
+        seed = 'diagonal' if g.N >= GDC_DIAGONAL_MIN_ROWS else 'operand'
+    if seed not in ('operand', 'diagonal'):
+        raise ValueError("diffusion_block: seed %r (operand | diagonal)" % (seed,))
+    N, j0, ncols = g.N, int(j0), int(ncols)
+    if not (0 <= j0 and 1 <= ncols and j0 + ncols <= N):
+        raise ValueError("diffusion_block: columns [%d, %d) outside [0, %d)" % (j0, j0 + ncols, N))
+    dev = w.device
+    if seed == 'operand':
+        E = _seed_block(N, j0, ncols, dev)
+        cur = E * schedule.init
+    else:  # no E_J at all: the start is init on the block's diagonal
+        E = None
+        cur = torch.zeros(N, ncols, dtype=torch.float32, device=dev)
+        cur[j0:j0 + ncols].fill_diagonal_(schedule.init)
+    other = torch.empty_like(cur)
+    prev = None
+    for cb, cf, ce in schedule.steps:
+        if schedule.two_term:
+            out, base = (prev, prev) if prev is not None else (other, None)
+        else:
+            out, base = other, None
+        terms = [(E, ce)] if seed == 'operand' else []
+        spmm_rhs(g, w, cur, rhs=False, stage=Stage(outs=[(out, base, cb if base is not None else 0.0, cf, terms)]))
+        if seed == 'diagonal':
+            out[j0:j0 + ncols].diagonal().add_(ce)
+        if schedule.two_term:
+            prev, cur = cur, out
+        else:
+            cur, other = out, cur
+    return cur
+
+
+def diffusion_block_torch(T, j0, ncols, schedule, dtype=torch.float32):
+    """diffusion_block in torch ops: T a torch sparse (or dense) [N, N] matrix."""
+    N = T.shape[0]
+    E = _seed_block(N, j0, ncols, T.device, dtype)
+    cur, prev = E * schedule.init, None
+    mm = torch.sparse.mm if T.layout != torch.strided else torch.matmul
+    for cb, cf, ce in schedule.steps:
+        nxt = cf * mm(T, cur) + ce * E
+        if schedule.two_term and prev is not None:
+            nxt = nxt + cb * prev
+        prev, cur = cur, nxt
+    return cur
+
+
+def _gdc_edges(edge_index, w, N, name):
+    if not isinstance(edge_index, torch.Tensor) or edge_index.dtype != torch.int64:
+        raise TypeError("%s: edge_index must be an int64 tensor" % name)
+    ei = edge_index
+    if ei.dim() == 3:
+        if ei.shape[0] != 1:
+            raise NotImplementedError("gnpde: %s: the rewired edge count differs per graph; only B = 1 is supported"
+                                      % name)
+        ei = ei[0]
+    if ei.dim() != 2 or ei.shape[0] != 2:
+        raise ValueError("%s: edge_index must be [2,E] or [1,2,E], got %s" % (name, tuple(edge_index.shape)))
+    E = ei.shape[1]
+    if w is None:
+        w = torch.ones(E, dtype=torch.float32, device=ei.device)
+    else:
+        if w.dtype != torch.float32:
+            raise TypeError("gnpde: %s: weights must be torch.float32, got %s" % (name, w.dtype))
+        w = w.reshape(-1)
+        if w.numel() != E:
+            raise ValueError("%s: %d weights for %d edges" % (name, w.numel(), E))
+    if E and (int(ei.min()) < 0 or int(ei.max()) >= N):
+        raise IndexError("%s: edge_index values must be in [0, %d)" % (name, N))
+    return ei[0], ei[1], w
+
+
+def _coalesce_sum(row, col, w, N):
+    """(row, col, w) -> sorted by (row, col), duplicates summed one after another in COO
+    order (no atomics: every pass adds to distinct positions)."""
+    if row.numel() == 0:
+        return row, col, w
+    key = row * N + col
+    skey, order = torch.sort(key, stable=True)
+    ws = w[order]
+    first = torch.ones_like(skey, dtype=torch.bool)
+    first[1:] = skey[1:] != skey[:-1]
+    uid = torch.cumsum(first, 0) - 1
+    pos = torch.arange(skey.numel(), device=skey.device)
+    start = torch.zeros(int(uid[-1]) + 1, dtype=torch.int64, device=skey.device)
+    start[uid[first]] = pos[first]
+    rank = pos - start[uid]
+    val = torch.zeros(start.numel(), dtype=w.dtype, device=w.device)
+    for r in range(int(rank.max()) + 1):
+        sel = rank == r
+        val[uid[sel]] += ws[sel]
+    ukey = skey[first]
+    return torch.div(ukey, N, rounding_mode='floor'), ukey % N, val
+
+
+def _last_self_loops(row, col, w, N, fill):
+    """add_remaining_self_loops as ops.add_self_loops reads it: the non-loop edges, then one
+    loop per node with its last existing loop's weight, or ``fill``."""
+    loop = row == col
+    pos = torch.arange(row.numel(), device=row.device)
+    last = torch.full((N,), -1, dtype=torch.int64, device=row.device)
+    if bool(loop.any()):
+        last = last.scatter_reduce(0, row[loop], pos[loop], 'amax', include_self=True)
+    lw = torch.full((N,), float(fill), dtype=w.dtype, device=w.device)
+    has = last >= 0
+    lw[has] = w[last[has]]
+    nodes = torch.arange(N, device=row.device)
+    return torch.cat([row[~loop], nodes]), torch.cat([col[~loop], nodes]), torch.cat([w[~loop], lw])
+
+
+def gdc_matrix(edge_index, w, N, self_loop_weight=1.0, remaining=False):
+    """Steps 1 and 2's input of the GDC contract, in torch ops on any device: M = coalesce(A) +
+    w_self I (remaining=False, PyG GDC.__call__) or A with the missing self loops filled
+    (remaining=True, GDCWrapper.position_encoding), coalesced and sorted by (row, col), and
+    checked symmetric on the device -> (row, col, val)."""
+    row, col, w = _gdc_edges(edge_index, w, N, "gdc")
+    ws = 0.0 if self_loop_weight is None else float(self_loop_weight)
+    if ws != 0.0:
+        if remaining:
+            row, col, w = _last_self_loops(row, col, w, N, ws)
+        else:
+            nodes = torch.arange(N, device=row.device)
+            row, col = torch.cat([row, nodes]), torch.cat([col, nodes])
+            w = torch.cat([w, torch.full((N,), ws, dtype=w.dtype, device=w.device)])
+    row, col, val = _coalesce_sum(row, col, w, N)
+    tkey, order = torch.sort(col * N + row)
+    if not (torch.equal(tkey, row * N + col) and torch.equal(val[order], val)):
+        raise ValueError("gdc: normalization_in='sym' needs a symmetric weighted graph (the iteration bounds rest "
+                         "on T's spectrum lying in [-1, 1]); symmetrise it first, e.g. with "
+                         "graph_rewiring.to_undirected")
+    return row, col, val
+
+
+def _gdc_schedule(method, alpha, t, tol):
+    return diffusion_schedule('ppr', alpha=alpha, tol=tol) if method == 'ppr' else \
+        diffusion_schedule('heat', t=t, tol=tol)
+
+
+def _gdc_check(N, sparsification, k, dense, max_bytes):
+    if dense:
+        if 4 * N * N > int(max_bytes):
+            raise ValueError("gdc: the dense [%d, %d] positional encoding takes %d bytes, above max_bytes=%d"
+                             % (N, N, 4 * N * N, int(max_bytes)))
+    elif sparsification == 'topk':
+        if int(k) < 1:
+            raise ValueError("gdc: gdc_k=%d must be >= 1" % int(k))
+        if int(k) > N:
+            raise ValueError("gdc: gdc_k=%d exceeds the %d nodes of the graph" % (int(k), N))
+    elif sparsification != 'threshold':
+        raise ValueError("gdc: sparsification %r (topk | threshold)" % (sparsification,))
+
+
+def _gdc_run(N, block_fn, topk_fn, sparsification, k, threshold, dense, block, dev):
+    """The per-block part shared by gdc and gdc_torch: block_fn(j0, ncols) -> Y [N, ncols]."""
+    if dense:
+        S = torch.empty(N, N, dtype=torch.float32, device=dev)
+    rows, cols, vals = [], [], []
+    for j0 in range(0, N, block):
+        ncols = min(block, N - j0)
+        Y = block_fn(j0, ncols)
+        if dense:
+            s = Y.sum(0, keepdim=True)
+            S[:, j0:j0 + ncols] = torch.where(s == 0, torch.zeros_like(Y), Y / s)
+        elif sparsification == 'topk':
+            idx, _val, wn = topk_fn(Y, k)
+            rows.append(idx.reshape(-1).to(torch.int64))
+            cols.append(torch.arange(j0, j0 + ncols, device=dev).repeat_interleave(k))
+            vals.append(wn.reshape(-1))
+        else:
+            keep = Y >= threshold
+            kept = torch.where(keep, Y, torch.zeros_like(Y))
+            s = kept.sum(0, keepdim=True)
+            wn = torch.where(s == 0, torch.zeros_like(Y), kept / s)
+            at = torch.nonzero(keep)
+            rows.append(at[:, 0])
+            cols.append(at[:, 1] + j0)
+            vals.append(wn[at[:, 0], at[:, 1]])
+    if dense:
+        return S
+    row, col, val = torch.cat(rows), torch.cat(cols), torch.cat(vals)
+    order = torch.argsort(row * N + col)
+    return torch.stack([row[order], col[order]]), val[order]
+
+
+def gdc(edge_index, w, N, method='ppr', alpha=0.05, t=3.0, self_loop_weight=1.0, sparsification='topk', k=64,
+        threshold=0.01, tol=1e-6, dense=False, max_bytes=GDC_MAX_BYTES, seed=None, block=GDC_BLOCK):
+    """Graph diffusion convolution of one symmetric graph on the device (the contract of
+    gnpde.graph_rewiring's docstring): M with self loops, T = D^-1/2 M D^-1/2 (ops.norm_weights,
+    GCN), then per block of ``block`` seed columns the diffusion recurrence on K1
+    (diffusion_block) and the column top-k (topk_cols) or the threshold, column-normalised.
+    -> (edge_index int64 [2, E] sorted by (row, col), weights fp32 [E]); dense=True (the
+    positional encoding; self loops by add_remaining_self_loops = ops.add_self_loops): the
+    column-normalised S, fp32 [N, N], at most max_bytes."""
+    N = int(N)
+    _require_gpu(edge_index, "edge_index", torch.int64)
+    if w is not None:
+        _require_gpu(w, "edge weights", torch.float32)
+    _gdc_check(N, sparsification, k, dense, max_bytes)
+    if sparsification == 'topk' and not dense and int(k) > TOPK_COLS_MAX_K:
+        raise ValueError("gdc: gdc_k=%d outside the kernel's range (1 <= k <= %d)" % (int(k), TOPK_COLS_MAX_K))
+    dev = edge_index.device
+    ws = 0.0 if self_loop_weight is None else float(self_loop_weight)
+    if dense and ws != 0.0:
+        row, col, wv = _gdc_edges(edge_index, w, N, "gdc")
+        ei, wl = add_self_loops(torch.stack([row, col]).unsqueeze(0), wv.unsqueeze(0), ws, N)
+        row, col, val = gdc_matrix(ei, wl.reshape(-1), N, 0.0)
+    else:
+        row, col, val = gdc_matrix(edge_index, w, N, ws)
+    ei = torch.stack([row, col]).unsqueeze(0).contiguous()
+    tw = norm_weights(ei, val.unsqueeze(0).contiguous(), N, _lib.NORM_GCN)
+    g = GraphCSR(ei, N, validate=False)
+    w_csr = g.gather_weights(tw)
+    sched = _gdc_schedule(method, alpha, t, tol)
+    return _gdc_run(N, lambda j0, nc: diffusion_block(g, w_csr, j0, nc, sched, seed=seed), topk_cols, sparsification,
+                    int(k), float(threshold), dense, int(block), dev)
+
+
+def gdc_torch(edge_index, w, N, method='ppr', alpha=0.05, t=3.0, self_loop_weight=1.0, sparsification='topk', k=64,
+              threshold=0.01, tol=1e-6, dense=False, max_bytes=GDC_MAX_BYTES, block=GDC_BLOCK):
+    """gdc restated in torch ops on any device (the host tests' path and the baseline of
+    tools/gdc_bench.py): the same schedules with torch.sparse.mm products in fp32, the
+    selection by topk_cols_torch.  The summation orders are torch's, not the kernels'."""
+    N = int(N)
+    _gdc_check(N, sparsification, k, dense, max_bytes)
+    row, col, val = gdc_matrix(edge_index, w, N, self_loop_weight, remaining=dense)
+    dev = val.device
+    deg = torch.zeros(N, dtype=torch.float32, device=dev).index_add_(0, col, val)
+    fac = deg.pow(-0.5)
+    fac = torch.where(torch.isinf(fac), torch.zeros_like(fac), fac)
+    T = torch.sparse_coo_tensor(torch.stack([row, col]), fac[row] * val * fac[col], (N, N)).coalesce()
+    sched = _gdc_schedule(method, alpha, t, tol)
+    return _gdc_run(N, lambda j0, nc: diffusion_block_torch(T, j0, nc, sched), topk_cols_torch, sparsification,
+                    int(k), float(threshold), dense, int(block), dev)

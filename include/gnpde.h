@@ -1088,6 +1088,27 @@ int gnpde_two_hop_fill_f32(const int32_t* rowptr, const int32_t* col, const floa
                            int64_t lds_max, int64_t n_waves, float* acc, uint32_t* bits, const int32_t* out_ptr,
                            int64_t nnz_out, int32_t* out_col, float* out_val, int64_t* out_ei, void* stream);
 
+/* ---------------------------------------------------------------- column top-k
+ * The sparsification of a GDC diffusion block (gnpde.ops.gdc; PyG GDC's `topk` with dim = 0,
+ * src/graph_rewiring.py:50-51; entry points added under ABI 8): for every column c < ncols
+ * of the row-major block y [N, ld] (fp32, finite values of either sign) the k entries that
+ * are largest in the total order (value descending, row ascending; -0 counts as +0), in that
+ * order:
+ *   idx_out [ncols, k] the rows, val_out [ncols, k] their values,
+ *   wnorm_out [ncols, k] (NULL: not written) = val / (val_0 + val_1 + ... + val_{k-1}), the
+ *   sum taken sequentially in rank order in fp32, 0 when the sum is 0.
+ * The rows are split into runs of rows_per_wg rows (rounded up to a multiple of 64; 0 = chosen
+ * from the shape) that workgroups scan on their own; with more than one run their sorted
+ * partial lists go through `workspace` (gnpde_topk_cols_workspace_bytes of the same N, ncols,
+ * k, rows_per_wg; 8-byte aligned) and are merged in the same key order, so the outputs do
+ * not depend on rows_per_wg.  No floating-point atomics: the same bits on every call.
+ * 1 <= k <= 128, otherwise GNPDE_EUNSUPPORTED; k > N or ncols > ld: GNPDE_EINVAL; all
+ * arguments are validated on the host before any launch.                              */
+size_t gnpde_topk_cols_workspace_bytes(int64_t N, int64_t ncols, int64_t k, int64_t rows_per_wg);
+int gnpde_topk_cols_f32(const float* y, int64_t N, int64_t ncols, int64_t ld, int64_t k, int32_t* idx_out,
+                        float* val_out, float* wnorm_out, int64_t rows_per_wg, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
