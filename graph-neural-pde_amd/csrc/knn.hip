@@ -9,42 +9,10 @@
 // the others per graph.  The main kernel gives one workgroup a tile of 64 queries of
 // one graph and lets it scan all N candidates of that graph in tiles of 128: there is
 // no merge across workgroups, so the result does not depend on the launch geometry.
-//
-// Distance tile: an "SGEMM with (a - b)^2 in place of a * b".  Chunks of 32 columns of
-// the query and the candidate rows are staged transposed in LDS ([column][row], rows
-// padded by 4 words: the 16-column x 2-row store pattern of a half wave is then 2-way on
-// the 32 store banks, which costs nothing, and the per-lane row reads are whole 16-byte
-// slots); a thread accumulates 4 queries x 8 candidates from three ds_read_b128 per
-// column.  The next chunk's global loads are issued before the current chunk's
-// arithmetic.  The last chunk is zero-padded on both sides, so padding adds exactly 0;
-// a short last chunk walks only its own columns.
-//
-// Selection: a query's current k smallest keys, sorted, live in LDS, one per lane of the
-// wave that owns the query; a key is (float bits of d) << 32 | j, and since d >= 0 the
-// unsigned integer order of the keys is the (d, j) order.  After a candidate tile its
-// 64 x 128 distances go to LDS (over the staging area), and every wave tests its 16
-// queries against their k-th key with lane = candidate: one compare and a ballot per
-// (query, half tile), without a branch, so the LDS reads pipeline.  Past the first
-// tiles almost no ballot is non-zero; those that are take a rank merge (every survivor
-// and every list entry computes its place in the union from ballots and writes itself
-// there), O(survivors) steps.  Masked candidates and the j >= N tail carry ~0.
-#include "common.hpp"
+// The distance tile and the selection are those of knn_tile.hpp (shared with posdist.hip).
+#include "knn_tile.hpp"
 
 namespace gnpde {
-
-constexpr int kKnnTQ = 64;            // queries of a workgroup
-constexpr int kKnnTJ = 128;           // candidates of a tile (two halves of one wave each)
-constexpr int kKnnCK = 32;            // columns of a staged chunk
-constexpr int kKnnLDQ = kKnnTQ + 4;   // LDS row strides of the transposed chunks (words)
-constexpr int kKnnLDC = kKnnTJ + 4;
-constexpr int kKnnMaxK = 64;          // one list entry per lane
-constexpr int kKnnQPerWave = kKnnTQ / kWavesPerBlock;  // 16 queries owned by a wave
-constexpr int kKnnQLoads = kKnnTQ * kKnnCK / kBlock;   // 8 staged words of the queries per thread
-constexpr int kKnnCLoads = kKnnTJ * kKnnCK / kBlock;   // 16 of the candidates
-constexpr int kKnnMaskRows = 8;       // rows a wave of the pre-pass walks
-constexpr unsigned long long kKnnNone = ~0ull;
-
-static_assert(kKnnCK * (kKnnLDQ + kKnnLDC) <= kKnnTQ * kKnnTJ, "the distance tile covers the staging area");
 
 // masked[b*N + r] = 1 when row r of graph b is all zero or holds a non-finite value;
 // n_valid[b] (zeroed by the caller) += the other rows.  One wave per row, 8 rows a wave.
@@ -71,44 +39,10 @@ __global__ __launch_bounds__(kBlock) void knn_mask_kernel(const float* __restric
   if (lane == 0 && cnt) atomicAdd(n_valid + b, cnt);
 }
 
-__device__ __forceinline__ unsigned long long knn_key(float d, int j, bool ok) {
-  return ok ? ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j : kKnnNone;
-}
-
-__device__ __forceinline__ unsigned long long knn_readlane(unsigned long long v, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, l);
-  const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// Merge the keys of one half tile that pass the query's k-th key into its sorted list
-// (lst[0..k), one entry per lane).  Keys are distinct (a candidate is scanned once), so
-// the place of a key in the union is the number of keys below it.
-__device__ __forceinline__ void knn_merge(unsigned long long* lst, unsigned long long key, int k, int lane) {
-  const unsigned long long thr = lst[k - 1];
-  const bool pass = key < thr;
-  unsigned long long m = __ballot(pass);
-  if (m == 0ull) return;
-  const unsigned long long L = lane < k ? lst[lane] : kKnnNone;
-  int below_L = 0, below_S = 0, list_below = 0;
-  while (m) {
-    const int s = __ffsll((long long)m) - 1;
-    m &= m - 1;
-    const unsigned long long sk = knn_readlane(key, s);
-    below_L += sk < L ? 1 : 0;    // survivors below this lane's list entry
-    below_S += sk < key ? 1 : 0;  // survivors below this lane's candidate
-    const int nl = __popcll(__ballot(L < sk));
-    if (lane == s) list_below = nl;
-  }
-  const int pl = lane + below_L;
-  if (pl < k) lst[pl] = L;        // lane >= k: pl >= k
-  if (pass) {
-    const int ps = list_below + below_S;
-    if (ps < k) lst[ps] = key;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-}
-
+// The kernel of gnpde_knn_f32 keeps its own, monolithic form of knn_tile.hpp's tile loop and
+// filter (the same statements; the helpers are the header's).  Written over dist_tile_sweep
+// and a functor, as pos_knn_kernel is, the same code allocates 268 - 277 registers where this
+// form takes 249: under 256 it runs two waves per SIMD, above it one.
 __global__ __launch_bounds__(kBlock) void knn_kernel(const float* __restrict__ x, int N, int C, int64_t ld, int k,
                                                      const uint8_t* __restrict__ masked,
                                                      int* __restrict__ idx_out, float* __restrict__ dist_out) {

@@ -19,7 +19,8 @@ from .function_transformer_attention import ODEFuncTransformerAtt, SpGraphTransA
 from .model_configurations import set_block, set_function  # noqa: F401
 from .integrator import odeint  # noqa: F401
 from .early_stop_solver import EarlyStopInt  # noqa: F401
-from .graph_rewiring import KNN, apply_KNN, GDCWrapper, apply_gdc  # noqa: F401
+from .graph_rewiring import (KNN, apply_KNN, GDCWrapper, apply_gdc, hyperbolize, apply_dist_KNN,  # noqa: F401
+                             apply_feat_KNN, apply_dist_threshold, apply_pos_dist_rewire)
 from .utils import MaxNFEException  # noqa: F401
 
 __version__ = "0.1.0"

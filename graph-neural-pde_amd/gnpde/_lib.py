@@ -190,6 +190,12 @@ SIGNATURES = {
     "gnpde_two_hop_fill_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "gnpde_topk_cols_workspace_bytes": (_size, [_i64, _i64, _i64, _i64]),
     "gnpde_topk_cols_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _size, _vp]),
+    "gnpde_pos_knn_workspace_bytes": (_size, [_i64, _i64]),
+    "gnpde_pos_knn_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "gnpde_pair_workspace_bytes": (_size, [_i64]),
+    "gnpde_pair_select_f32": (_int, [_vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _vp, _size, _vp]),
+    "gnpde_pair_threshold_count_f32": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _size, _vp]),
+    "gnpde_pair_threshold_fill_f32": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _size, _vp]),
 }
 
 # constants mirrored from include/gnpde.h
@@ -213,6 +219,8 @@ SCORE_GAT = 6
 NORM_RW_ROW = 0
 NORM_RW_COL = 1
 NORM_GCN = 2
+METRIC_EUCLID = 0
+METRIC_POINCARE = 1
 
 _lock = threading.Lock()
 _lib = None

@@ -1,4 +1,4 @@
-"""Graph rewiring: kNN and GDC.
+"""Graph rewiring: kNN, GDC and positional-encoding distances.
 
 kNN graph rewiring (the reference's ``rewire_KNN``; src/graph_rewiring.py:122-161, called
 from the training loop at src/graph_datasets/run_GNN.py:252-254): every
@@ -69,6 +69,27 @@ raises NotImplementedError): ``edge_index`` [2, E] or [1, 2, E] int64, optional 
 8. ``exact``.  DEPARTURE: both settings return the exact matrix to the tolerance above (the
    push approximation's own error is not reproduced).  ``exact=False`` with a self-loop
    weight other than 1 raises ValueError (the wrapper's assert).
+
+Positional-encoding distance rewiring (the reference's ``--rewiring pos_enc_knn``:
+``apply_pos_dist_rewire`` src/graph_rewiring.py:318-375 with ``hyperbolic_distances.hyperbolize``
+and ``distances_kNN``).  Those lines do not run with current numpy / scipy / sklearn; what is
+built is what they intend, per graph, for encodings x [N, C]:
+
+* d_ij = sum_c (x_ic - x_jc)^2 in fp32 (the difference form above); the rank value u_ij =
+  d_ij r_i r_j with r_i = 1 / max(1 - |x_i|^2, 2^-52) for ``pos_enc_type`` HYP* (|x|^2, 1 - |x|^2
+  and r in float64, r rounded to fp32 once), u_ij = d_ij for DW*.
+* Distances.  HYP*: D = arccosh(1 + 2u), the Poincare ball; DW*: D = sqrt(u).  Both are monotone
+  in u, so all ranking is done on u.
+* 'topk': row i -> the ``gdc_k`` columns of smallest (u_ij, j), the self index included (D_ii = 0,
+  sklearn's `precomputed` kNN); int64 [B, 2, N k], src = the row.  An all-zero row is the origin,
+  a point like any other; only a row with a non-finite value is masked, and it raises.
+* 'threshold': thr = numpy.quantile(D, quant) over all N^2 entries (linear interpolation, the
+  diagonal included); the edges are numpy.where(D <= thr): i ascending, j ascending within i.
+  With pos = quant (N^2 - 1) and lo = floor(pos), {D <= thr} = {u <= u_(lo)}: one order statistic,
+  found by a radix select over the matrix's tiles, which are recomputed by every pass and never
+  stored (csrc/posdist.hip).
+* DEPARTURES: the encodings are passed in (no pickle cache on disk), and the helpers
+  ``apply_dist_KNN`` / ``apply_dist_threshold`` take encodings, not a dense distance matrix.
 """
 import torch
 
@@ -220,4 +241,117 @@ def apply_gdc(data, opt, type="combined", gdc=None):
         if opt['pos_enc_orientation'] == "col":
             return wrapper.position_encoding(data).T
         raise ValueError("apply_gdc: pos_enc_orientation %r (row | col)" % (opt['pos_enc_orientation'],))
+    return data
+
+
+# --------------------------------------------------------------------------- positional-encoding distances
+def _metric_of(pos_enc_type):
+    t = str(pos_enc_type)
+    if t.startswith("HYP"):
+        return 'poincare'
+    if t.startswith("DW"):
+        return 'euclid'
+    raise ValueError("apply_pos_dist_rewire: pos_enc_type %r (HYP* | DW*)" % (pos_enc_type,))
+
+
+def hyperbolize(x, max_bytes=ops.POSDIST_MAX_BYTES):
+    """The dense Poincare distances of the encodings x [B, N, C] (or [N, C]): fp32 [B, N, N]
+    (the reference's hyperbolic_distances.hyperbolize, for small N: 4 B N^2 bytes above
+    max_bytes, 8 GiB, raises ValueError).  Plain torch on x's device; the rewiring itself never
+    forms this matrix."""
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    B, N, _C = x.shape
+    if 4 * B * N * N > int(max_bytes):
+        raise ValueError("hyperbolize: the dense [%d, %d, %d] distances take %d bytes, above max_bytes=%d"
+                         % (B, N, N, 4 * B * N * N, int(max_bytes)))
+    x = x.float()
+    out = torch.empty(B, N, N, dtype=torch.float32, device=x.device)
+    for b in range(B):
+        u = ops._pair_dense_u(x[b], ops._lib.METRIC_POINCARE, max_bytes, "hyperbolize")
+        out[b] = ops.pair_dist_from_u(u, 'poincare').float()
+    return out
+
+
+def apply_dist_KNN(x, k, metric='poincare', backend=None):
+    """The k nearest neighbours of every row of the encodings x [B, N, C] (or [N, C]) under
+    ``metric`` as an edge list: int64 [B, 2, N k], src = the row (position i k + m -> i), dst its
+    neighbours in ascending (distance, index), the self index included (sklearn's `precomputed`
+    kNN of the reference's apply_dist_KNN).  DEPARTURE: takes the encodings, not a dense
+    distance matrix.  A row with a non-finite value, or k above N, raises ValueError (the one
+    host read: the pre-pass's counts)."""
+    be = ops.POSDIST_HIP if backend is None else backend
+    k = int(k)
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    with torch.no_grad():
+        idx, n_valid = be.pos_knn(x, k, metric)
+        B, N = idx.shape[0], idx.shape[1]
+        short = int(n_valid.min())  # the host read
+        if short < N:
+            raise ValueError("apply_dist_KNN: %d rows of a graph hold a non-finite value" % (N - short))
+        first = torch.arange(N, device=idx.device, dtype=torch.int64).repeat_interleave(k).expand(B, N * k)
+        return torch.stack([first, idx.reshape(B, N * k).to(torch.int64)], dim=1)
+
+
+def apply_feat_KNN(x, k, backend=None):
+    """The reference's apply_feat_KNN: apply_dist_KNN under the Euclidean metric."""
+    return apply_dist_KNN(x, k, metric='euclid', backend=backend)
+
+
+def apply_dist_threshold(x, quant=1 / 1000, metric='poincare', backend=None):
+    """Every pair of rows of the encodings x [N, C] (or [1, N, C]) whose distance is at most
+    numpy.quantile(D, quant) of all N^2 distances (linear interpolation, the diagonal included):
+    int64 [1, 2, E] in numpy.where order, src = the row.  DEPARTURE: takes the encodings, not a
+    dense distance matrix.  B > 1 raises NotImplementedError (the edge counts differ per graph);
+    quant outside [0, 1], a non-finite value or E >= 2^35 raises ValueError."""
+    be = ops.POSDIST_HIP if backend is None else backend
+    quant = float(quant)
+    if not 0.0 <= quant <= 1.0:
+        raise ValueError("apply_dist_threshold: quantile %r outside [0, 1]" % (quant,))
+    if x.dim() == 3 and x.shape[0] != 1:
+        raise NotImplementedError("apply_dist_threshold with B > 1: the edge counts differ per graph")
+    with torch.no_grad():
+        return be.threshold_edges(x, quant, metric).unsqueeze(0)
+
+
+def apply_pos_dist_rewire(data, opt, pos_encoding, backend=None):
+    """The reference's apply_pos_dist_rewire (src/graph_rewiring.py:318-375; ``--rewiring
+    pos_enc_knn``): the graph becomes the gdc_k nearest neighbours of every node's positional
+    encoding, or every pair within the pos_dist_quantile quantile of all N^2 distances.
+
+    pos_encoding: [N, C] or [1, N, C] fp32 on the device, required.  DEPARTURE: the encodings
+    are passed in; the reference's pickle cache of encodings and distances on disk is out of
+    scope, like every loader.  The dense distance matrix is never formed.
+    Options read: pos_enc_type (HYP*: Poincare distances; DW*: Euclidean; anything else raises
+    ValueError), gdc_sparsification ('topk' with gdc_k <= 64 | 'threshold'), pos_dist_quantile
+    (HYP* only: for DW* the reference passes no quantile to apply_dist_threshold, which then
+    takes its default of 1/1000 — kept).
+    Writes data.edge_index at the rank it came in ([2, E], or [1, 2, E]) and returns data;
+    data.edge_attr, the weights of edges that no longer exist, becomes None.
+    Raises: NotImplementedError for B > 1 under 'threshold'; ValueError for a row with a
+    non-finite value, a quantile outside [0, 1], gdc_k outside [1, min(64, N)], or E >= 2^35
+    (before the edge list is allocated).  backend: ops.POSDIST_HIP by default; ops.POSDIST_TORCH
+    is the same contract in torch ops on any device."""
+    metric = _metric_of(opt['pos_enc_type'])
+    x = pos_encoding
+    sp = opt['gdc_sparsification']
+    if sp == 'topk':
+        k = int(opt['gdc_k'])
+        if not 1 <= k <= ops.KNN_MAX_K:
+            raise ValueError("apply_pos_dist_rewire: gdc_k=%d outside [1, %d]" % (k, ops.KNN_MAX_K))
+        ei = apply_dist_KNN(x, k, metric, backend)
+    elif sp == 'threshold':
+        quant = opt['pos_dist_quantile'] if metric == 'poincare' else 1 / 1000
+        ei = apply_dist_threshold(x, quant, metric, backend)
+    else:
+        raise ValueError("apply_pos_dist_rewire: gdc_sparsification %r (topk | threshold)" % (sp,))
+    old = data.edge_index
+    batched = old is not None and old.dim() == 3
+    if not batched:
+        if ei.shape[0] != 1:
+            raise ValueError("apply_pos_dist_rewire: B = %d encodings for an unbatched edge_index" % ei.shape[0])
+        ei = ei[0]
+    data.edge_index = ei
+    data.edge_attr = None
     return data

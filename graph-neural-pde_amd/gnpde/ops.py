@@ -3119,3 +3119,275 @@ def gdc_torch(edge_index, w, N, method='ppr', alpha=0.05, t=3.0, self_loop_weigh
     sched = _gdc_schedule(method, alpha, t, tol)
     return _gdc_run(N, lambda j0, nc: diffusion_block_torch(T, j0, nc, sched), topk_cols_torch, sparsification,
                     int(k), float(threshold), dense, int(block), dev)
+
+
+# --------------------------------------------------------------------------- positional-encoding distances
+# (pos_enc_knn rewiring: csrc/posdist.hip; the contract is in gnpde.graph_rewiring's docstring)
+POSDIST_MAX_BYTES = GDC_MAX_BYTES  # the dense fp32 [N, N] matrix of the torch restatements
+POSDIST_MAX_EDGES = (1 << 31) * 16  # pair_threshold_edges: edges of one edge list
+POINCARE_EPS = 2.0 ** -52  # float64 eps, the reference's clamp of 1 - |x|^2
+_METRICS = {'euclid': _lib.METRIC_EUCLID, 'euclidean': _lib.METRIC_EUCLID, 'poincare': _lib.METRIC_POINCARE,
+            'hyperbolic': _lib.METRIC_POINCARE, _lib.METRIC_EUCLID: _lib.METRIC_EUCLID,
+            _lib.METRIC_POINCARE: _lib.METRIC_POINCARE}
+
+
+def _metric(metric, name):
+    try:
+        return _METRICS[metric.lower() if isinstance(metric, str) else metric]
+    except KeyError:
+        raise ValueError("%s: metric %r ('euclid' | 'poincare')" % (name, metric))
+
+
+def pair_rank(N, quant):
+    """(lo, hi, frac): numpy.quantile's position among M = N^2 sorted values for the linear
+    method — its virtual index (M - 1) q, one float64 product (M - 1 is exact in float64 for
+    N <= 2^26), lo = floor, hi = min(lo + 1, M - 1), frac = index - lo (0 when hi == lo).  Pure host arithmetic in Python ints and floats."""
+    N, q = int(N), float(quant)
+    if N < 1:
+        raise ValueError("pair_rank: N=%d must be >= 1" % N)
+    if not 0.0 <= q <= 1.0:     # (a NaN fails both comparisons)
+        raise ValueError("pair_rank: quantile %r outside [0, 1]" % (quant,))
+    M = N * N
+    pos = float(M - 1) * q
+    lo = min(max(int(math.floor(pos)), 0), M - 1)
+    hi = min(lo + 1, M - 1)
+    frac = pos - math.floor(pos) if hi > lo else 0.0
+    return lo, hi, frac
+
+
+def pair_dist_from_u(u, metric):
+    """The distance of a rank value, in float64: sqrt(u) (euclid) or arccosh(1 + 2u) =
+    log1p(2u + 2 sqrt(u (u + 1))) (poincare)."""
+    u = u.double()
+    if _metric(metric, "pair_dist_from_u") == _lib.METRIC_EUCLID:
+        return torch.sqrt(u)
+    return torch.log1p(2.0 * u + 2.0 * torch.sqrt(u * (u + 1.0)))
+
+
+def _quantile_lerp(a, b, frac):
+    """numpy's _lerp of two float64 scalars (frac a host float)."""
+    if frac == 0.0:
+        return a
+    d = b - a
+    return b - d * (1.0 - frac) if frac >= 0.5 else a + d * frac
+
+
+def _pos_r(x, metric):
+    """r of the rank value u_ij = d_ij r_i r_j for the rows of x [..., N, C]: fp32 [..., N]; |x|^2,
+    1 - |x|^2 and the reciprocal in float64, one rounding to fp32 (as the pre-pass of
+    csrc/posdist.hip)."""
+    if metric == _lib.METRIC_EUCLID:
+        return torch.ones(x.shape[:-1], dtype=torch.float32, device=x.device)
+    q = (x.double() ** 2).sum(-1)
+    return (1.0 / torch.clamp_min(1.0 - q, POINCARE_EPS)).float()
+
+
+def _pair_u_rows(x, r, r0, r1):
+    """fp32 rank values u [r1 - r0, N] of the rows r0 .. r1 of one graph x [N, C]; NaN -> +inf."""
+    d = ((x[r0:r1, None, :] - x[None, :, :]) ** 2).sum(-1)
+    u = d * (r[r0:r1, None] * r[None, :])
+    return torch.where(torch.isnan(u), torch.full_like(u, float("inf")), u)
+
+
+def pos_knn_torch(x, k, metric, return_dist=False, chunk_bytes=None):
+    """gnpde_pos_knn_f32 restated in torch ops (any device; chunked over query rows): the k
+    smallest (u, j) keys of every row in ascending order, only rows with a non-finite value
+    masked (they return themselves; an all-zero row is the origin).  -> (idx int32 [B, N, k],
+    n_valid int32 [B]) or (idx, dist fp32 [B, N, k], n_valid), dist the distance itself."""
+    x = _knn_input(x, "pos_knn_torch")
+    m = _metric(metric, "pos_knn_torch")
+    k = int(k)
+    B, N, C = x.shape
+    if k < 1:
+        raise ValueError("pos_knn_torch: k=%d must be >= 1" % k)
+    if k > N:
+        raise ValueError("pos_knn_torch: k=%d exceeds the %d rows of a graph" % (k, N))
+    dev = x.device
+    masked = ~torch.isfinite(x).all(dim=-1)
+    n_valid = (~masked).sum(dim=1).to(torch.int32)
+    xs = torch.where(masked.unsqueeze(-1), torch.zeros_like(x), x)
+    r = _pos_r(xs, m)
+    idx = torch.empty(B, N, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(B, N, k, dtype=torch.float32, device=dev) if return_dist else None
+    j = torch.arange(N, dtype=torch.int64, device=dev)
+    none = torch.iinfo(torch.int64).max
+    rows = max(1, min(N, int(chunk_bytes or KNN_TORCH_BYTES) // max(1, 4 * N * C)))
+    for b in range(B):
+        for r0 in range(0, N, rows):
+            r1 = min(N, r0 + rows)
+            u = _pair_u_rows(xs[b], r[b], r0, r1)
+            key = (u.view(torch.int32).to(torch.int64) << 32) | j
+            key = torch.where(masked[b].unsqueeze(0), torch.full_like(key, none), key)
+            top = torch.topk(key, k, dim=1, largest=False, sorted=True).values
+            pad = top == none
+            idx[b, r0:r1] = torch.where(pad, torch.full_like(top, -1), top & 0xFFFFFFFF).to(torch.int32)
+            if return_dist:
+                uu = (top >> 32).to(torch.int32).view(torch.float32)
+                dd = pair_dist_from_u(uu, m).float()
+                dist[b, r0:r1] = torch.where(pad, torch.full_like(dd, float("inf")), dd)
+        own = torch.arange(N, dtype=torch.int32, device=dev).unsqueeze(1).expand(N, k)
+        idx[b] = torch.where(masked[b].unsqueeze(1), own, idx[b])
+        if return_dist:
+            dist[b] = torch.where(masked[b].unsqueeze(1), torch.zeros_like(dist[b]), dist[b])
+    return (idx, dist, n_valid) if return_dist else (idx, n_valid)
+
+
+def pos_knn(x, k, metric, return_dist=False):
+    """gnpde_pos_knn_f32: the k nearest rows of every row of x [B, N, C] (or [N, C]: B = 1, device
+    fp32) within its graph under ``metric`` ('euclid' | 'poincare'), in ascending (u, j), the self
+    index included.  Returns (idx int32 [B, N, k], n_valid int32 [B]) or (idx, dist fp32 [B, N, k],
+    n_valid), dist the distance itself (sqrt(u) | arccosh(1 + 2u)); nothing is read back here.
+    Only a row with a non-finite value is masked (never a neighbour, returns its own index).
+    1 <= k <= 64 (the kernel's range), k <= N."""
+    x = _knn_input(x, "pos_knn")
+    _require_gpu(x, "x", torch.float32)
+    m = _metric(metric, "pos_knn")
+    x = x.contiguous()
+    k = int(k)
+    B, N, C = x.shape
+    if k < 1:
+        raise ValueError("pos_knn: k=%d must be >= 1" % k)
+    if k > N:
+        raise ValueError("pos_knn: k=%d exceeds the %d rows of a graph" % (k, N))
+    if k > KNN_MAX_K:
+        raise ValueError("pos_knn: k=%d outside the kernel's range (1 <= k <= %d)" % (k, KNN_MAX_K))
+    dev = x.device
+    idx = torch.empty(B, N, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(B, N, k, dtype=torch.float32, device=dev) if return_dist else None
+    n_valid = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(_lib.fn("gnpde_pos_knn_workspace_bytes")(B, N)), dtype=torch.uint8, device=dev)
+    _lib.call("gnpde_pos_knn_f32", _ptr(x), B, N, C, C, k, m, _ptr(idx), _ptr(dist), _ptr(n_valid), _ptr(ws),
+              _stream(dev))
+    return (idx, dist, n_valid) if return_dist else (idx, n_valid)
+
+
+def _pair_input(x, name):
+    x = _knn_input(x, name)
+    if x.shape[0] != 1:
+        raise NotImplementedError("%s: one graph (B = 1), got B = %d: the edge counts differ per graph"
+                                  % (name, x.shape[0]))
+    return x[0]
+
+
+def _pair_dense_u(x, m, max_bytes, name):
+    N, C = x.shape
+    if 4 * N * N > int(max_bytes):
+        raise ValueError("%s: the dense [%d, %d] matrix takes %d bytes, above max_bytes=%d"
+                         % (name, N, N, 4 * N * N, int(max_bytes)))
+    r = _pos_r(x, m)
+    u = torch.empty(N, N, dtype=torch.float32, device=x.device)
+    rows = max(1, min(N, KNN_TORCH_BYTES // max(1, 4 * N * C)))
+    for r0 in range(0, N, rows):
+        u[r0:r0 + rows] = _pair_u_rows(x, r, r0, min(N, r0 + rows))
+    return u
+
+
+def pair_quantile_torch(x, quant, metric, max_bytes=POSDIST_MAX_BYTES):
+    """pair_quantile restated in torch ops on any device, on the dense fp32 [N, N] rank values
+    (at most max_bytes, else ValueError): -> (thr float64 scalar, u_lo fp32 scalar, count_le
+    int64 scalar)."""
+    x = _pair_input(x, "pair_quantile_torch")
+    m = _metric(metric, "pair_quantile_torch")
+    lo, hi, frac = pair_rank(x.shape[0], quant)
+    flat = _pair_dense_u(x, m, max_bytes, "pair_quantile_torch").reshape(-1)
+    u_lo = torch.kthvalue(flat, lo + 1).values
+    u_hi = torch.kthvalue(flat, hi + 1).values if (hi > lo and frac != 0.0) else u_lo
+    thr = _quantile_lerp(pair_dist_from_u(u_lo, m), pair_dist_from_u(u_hi, m), frac)
+    return thr, u_lo, (flat <= u_lo).sum()
+
+
+def pair_threshold_edges_torch(x, quant, metric, max_bytes=POSDIST_MAX_BYTES):
+    """pair_threshold_edges restated in torch ops on any device (dense, at most max_bytes)."""
+    x = _pair_input(x, "pair_threshold_edges_torch")
+    m = _metric(metric, "pair_threshold_edges_torch")
+    lo = pair_rank(x.shape[0], quant)[0]
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("pair_threshold_edges_torch: x holds a non-finite value")
+    u = _pair_dense_u(x, m, max_bytes, "pair_threshold_edges_torch")
+    u_lo = torch.kthvalue(u.reshape(-1), lo + 1).values
+    return torch.nonzero(u <= u_lo).t().contiguous()
+
+
+def _pair_ws(x):
+    N = x.shape[0]
+    nbytes = int(_lib.fn("gnpde_pair_workspace_bytes")(N))
+    return torch.empty(nbytes, dtype=torch.uint8, device=x.device), nbytes
+
+
+def _pair_gpu_input(x, metric, name):
+    x = _pair_input(x, name)
+    _require_gpu(x, "x", torch.float32)
+    return x.contiguous(), _metric(metric, name)
+
+
+def pair_select(x, rank, metric, ws=None):
+    """gnpde_pair_select_f32: (u fp32 [1], count_le int64 [1]) on the device — the rank value of
+    0-based rank ``rank`` among the N^2 entries of one graph x [N, C], and the number of entries
+    <= it.  Nothing is read back."""
+    x, m = _pair_gpu_input(x, metric, "pair_select")
+    N, C = x.shape
+    rank = int(rank)
+    if not 0 <= rank < N * N:
+        raise ValueError("pair_select: rank=%d must be in [0, N^2=%d)" % (rank, N * N))
+    buf, nbytes = ws if ws is not None else _pair_ws(x)
+    u = torch.empty(1, dtype=torch.float32, device=x.device)
+    cnt = torch.empty(1, dtype=torch.int64, device=x.device)
+    _lib.call("gnpde_pair_select_f32", _ptr(x), N, C, C, m, rank, _ptr(u), _ptr(cnt), _ptr(buf), nbytes,
+              _stream(x.device))
+    return u, cnt
+
+
+def pair_quantile(x, quant, metric):
+    """numpy.quantile(D, quant) over all N^2 pairwise distances of x [N, C] (device fp32; linear
+    interpolation) without the matrix: -> (thr float64 device scalar, u_lo fp32 [1], count_le
+    int64 [1]), u_lo the rank value of position lo = floor(quant (N^2 - 1)) and count_le the
+    number of entries <= it ({D <= thr} = {u <= u_lo}).  One select for lo and, when the position
+    is fractional, one for lo + 1; nothing is read back."""
+    x, m = _pair_gpu_input(x, metric, "pair_quantile")
+    lo, hi, frac = pair_rank(x.shape[0], quant)
+    ws = _pair_ws(x)
+    u_lo, cnt = pair_select(x, lo, m, ws)
+    u_hi = pair_select(x, hi, m, ws)[0] if (hi > lo and frac != 0.0) else u_lo
+    thr = _quantile_lerp(pair_dist_from_u(u_lo[0], m), pair_dist_from_u(u_hi[0], m), frac)
+    return thr, u_lo, cnt
+
+
+def pair_threshold_edges(x, quant, metric):
+    """Every pair (i, j) of x [N, C] (device fp32, one graph) whose distance is at most
+    numpy.quantile of all N^2 distances at ``quant``: edge_index int64 [2, E] in numpy.where
+    order (i ascending, j ascending within i).  One select, a count pass, torch's cumsum and a
+    fill pass; one host read (E, with the non-finite check) to allocate.  A non-finite value in
+    x, or E >= 2^35, raises ValueError."""
+    x, m = _pair_gpu_input(x, metric, "pair_threshold_edges")
+    N, C = x.shape
+    dev = x.device
+    lo = pair_rank(N, quant)[0]
+    ws = _pair_ws(x)
+    u_lo, _cnt = pair_select(x, lo, m, ws)
+    row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    row_count = row_ptr[1:]
+    _lib.call("gnpde_pair_threshold_count_f32", _ptr(x), N, C, C, m, _ptr(u_lo), _ptr(row_count), _ptr(ws[0]), ws[1],
+              _stream(dev))
+    row_count.cumsum_(0)     # row_ptr: the exclusive scan, row_ptr[N] the total
+    bad = (~torch.isfinite(x)).sum()
+    E, nbad = torch.stack([row_ptr[N], bad]).tolist()   # the host read
+    if nbad:
+        raise ValueError("pair_threshold_edges: x holds %d non-finite values" % nbad)
+    if E >= POSDIST_MAX_EDGES:
+        raise ValueError("pair_threshold_edges: %d edges, above the limit of %d" % (E, POSDIST_MAX_EDGES))
+    ei = torch.empty(2, E, dtype=torch.int64, device=dev)
+    _lib.call("gnpde_pair_threshold_fill_f32", _ptr(x), N, C, C, m, _ptr(u_lo), _ptr(row_ptr), E, _ptr(ei),
+              _ptr(ws[0]), ws[1], _stream(dev))
+    return ei
+
+
+class PosDistBackend(object):
+    """The two searches gnpde.graph_rewiring's positional-distance rewiring runs on."""
+
+    def __init__(self, pos_knn, threshold_edges):
+        self.pos_knn = pos_knn
+        self.threshold_edges = threshold_edges
+
+
+POSDIST_HIP = PosDistBackend(pos_knn, pair_threshold_edges)
+POSDIST_TORCH = PosDistBackend(pos_knn_torch, pair_threshold_edges_torch)

@@ -1109,6 +1109,53 @@ int gnpde_topk_cols_f32(const float* y, int64_t N, int64_t ncols, int64_t ld, in
                         float* val_out, float* wnorm_out, int64_t rows_per_wg, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- positional-encoding distances
+ * The pos_enc_knn rewiring (gnpde.graph_rewiring.apply_pos_dist_rewire,
+ * src/graph_rewiring.py:318-375; entry points added under ABI 8).  With d_ij = sum_c (x_ic -
+ * x_jc)^2 in fp32 (the difference form of gnpde_knn_f32) the rank value of a pair is
+ *   u_ij = d_ij (r_i r_j),   r_i = 1 / max(1 - |x_i|^2, 2^-52)  (GNPDE_METRIC_POINCARE; |x|^2,
+ *                            1 - |x|^2 and r in fp64, r rounded to fp32 once)
+ *                            r_i = 1                             (GNPDE_METRIC_EUCLID)
+ * and the distance D = arccosh(1 + 2 u) (Poincare) or sqrt(u) (Euclid) is monotone in it: all
+ * ranking is done on the fp32 u.  u_ij and u_ji are bit-equal, and every entry point below
+ * computes the same bits for a pair.  The [N, N] matrix is never stored.
+ *
+ * gnpde_pos_knn_f32: the contract of gnpde_knn_f32 (ascending (u, j), the self index a
+ * candidate, 1 <= k <= 64) except that only a row with a non-finite value is masked (an
+ * all-zero row is the origin, a point like any other) and that dist_out (or NULL) holds D:
+ * sqrt(u), or log1p(2 u + 2 sqrt(u (u + 1))).  workspace: gnpde_pos_knn_workspace_bytes(B, N)
+ * bytes, 16-byte aligned (the masks and r).
+ *
+ * gnpde_pair_select_f32 (one graph): *u_out = the u of 0-based rank `rank` among all N^2
+ * entries in ascending order, the diagonal included; *count_le_out = the number of entries
+ * with u <= *u_out.  A most-significant-first radix select on the bits of u (digits of 11, 11
+ * and 10 bits: three sweeps over the tiles on and above the diagonal); all counts are 64-bit
+ * integers and only integer atomics are used: the same bits on every call.  An entry of a row
+ * with a non-finite value ranks as +inf.
+ *
+ * gnpde_pair_threshold_count_f32: row_count[i] = #{j : u_ij <= *u_thr}.
+ * gnpde_pair_threshold_fill_f32: with row_ptr [N] the exclusive scan of row_count and E its
+ * total, ei_out [2, E] (int64) = the pairs (i, j) with u_ij <= *u_thr, i ascending and j
+ * ascending within i (numpy.where order): ei_out[0] the rows, ei_out[1] the columns.
+ *
+ * workspace of the three pair entry points: gnpde_pair_workspace_bytes(N) bytes, 16-byte
+ * aligned, linear in N (r, one 2048-bin histogram, the select's state).  1 <= N <= 2^24 (N =
+ * 0: nothing to do, except for the select), else GNPDE_EUNSUPPORTED; all arguments are
+ * validated on the host before any launch.                                              */
+#define GNPDE_METRIC_EUCLID 0
+#define GNPDE_METRIC_POINCARE 1
+size_t gnpde_pos_knn_workspace_bytes(int64_t B, int64_t N);
+int gnpde_pos_knn_f32(const float* x, int64_t B, int64_t N, int64_t C, int64_t ld, int64_t k, int metric,
+                      int32_t* idx_out, float* dist_out, int32_t* n_valid, void* workspace, void* stream);
+size_t gnpde_pair_workspace_bytes(int64_t N);
+int gnpde_pair_select_f32(const float* x, int64_t N, int64_t C, int64_t ld, int metric, int64_t rank, float* u_out,
+                          int64_t* count_le_out, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_pair_threshold_count_f32(const float* x, int64_t N, int64_t C, int64_t ld, int metric, const float* u_thr,
+                                   int64_t* row_count, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_pair_threshold_fill_f32(const float* x, int64_t N, int64_t C, int64_t ld, int metric, const float* u_thr,
+                                  const int64_t* row_ptr, int64_t E, int64_t* ei_out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
