@@ -7,6 +7,8 @@ C ABI of include/gnpde.h (libgnpde.so, loaded by gnpde._lib with no fallback).
 """
 from . import _lib, ops  # noqa: F401
 from .base_classes import GraphData, ODEblock, ODEFunc  # noqa: F401
+from .regularized_ODE_function import (RegularizedODEfunc, create_regularization_fns,  # noqa: F401
+                                       directional_derivative, quadratic_cost)
 from .block_constant import ConstantODEblock  # noqa: F401
 from .block_mixed import MixedODEblock  # noqa: F401
 from .block_transformer_hard_attention import HardAttODEblock  # noqa: F401

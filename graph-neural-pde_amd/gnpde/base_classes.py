@@ -32,6 +32,8 @@ from torch import nn
 from . import ops
 from ._cache import _tensor_key  # noqa: F401  (re-exported for the function modules)
 from .integrator import odeint, odeint_adjoint
+from .regularized_ODE_function import (OPT_KEY as REG_OPT_KEY, RegularizedODEfunc,  # noqa: F401  (re-exported)
+                                       create_regularization_fns, not_opted_in)
 from .utils import get_rw_adj, gcn_norm_fill_val
 
 
@@ -181,20 +183,6 @@ class ODEFunc(nn.Module):
         return self.__class__.__name__
 
 
-class RegularizedODEfunc(nn.Module):
-    """Holder with the reference's ``reg_odefunc.odefunc`` attribute path
-    (src/regularized_ODE_function.py).  The kinetic-energy / Jacobian
-    regularisers are OUT OF SCOPE (off by default, broken in the fork)."""
-
-    def __init__(self, odefunc, regularization_fns):
-        super(RegularizedODEfunc, self).__init__()
-        self.odefunc = odefunc
-        self.regularization_fns = regularization_fns
-
-    def forward(self, t, state):
-        raise NotImplementedError("gnpde: ODE regularisation terms are out of scope (SURVEY.md §2 row 12)")
-
-
 class ODEblock(nn.Module):
     """src/base_classes.py:33-98."""
 
@@ -280,7 +268,9 @@ class ODEblock(nn.Module):
 
     def _integrate(self, x, options):
         if self.training and self.nreg > 0:
-            raise NotImplementedError("gnpde: ODE regularisation terms are out of scope (SURVEY.md §2 row 12)")
+            if not self.opt.get(REG_OPT_KEY):
+                raise not_opted_in("a training forward with %d regularization_fns" % self.nreg)
+            return self._integrate_regularized(x, options)
         integrator = self.train_integrator if self.training else self.test_integrator
         t = self.t.type_as(x)
         # opt-in: explicit_adams / implicit_adams (gnpde.integrator); opt['max_order'], when given, goes
@@ -303,6 +293,19 @@ class ODEblock(nn.Module):
             state_dt = integrator(self.odefunc, x, t, method=self.opt['method'], options=options, atol=self.atol,
                                   rtol=self.rtol)
         return state_dt[1]
+
+    def _integrate_regularized(self, x, options):
+        """A training forward with regularisers (src/block_constant.py:27-54 as meant): the state
+        (x, r_1, ..., r_nreg), every r_j [B,N] zero at t[0]; returns (z, (r_1(T), ...)).  The solve
+        integrates the block's own ``odefunc`` (gnpde.regularized_ODE_function.RegularizedODEfunc);
+        the integrators name the cases they do not take (adjoint, adaptive and multistep methods)."""
+        t = self.t.type_as(x)
+        if self.opt.get('gnpde_adams'):
+            options = dict(options, gnpde_adams=True)
+        state = (x,) + tuple(torch.zeros(x.shape[:-1], dtype=x.dtype, device=x.device) for _ in range(self.nreg))
+        out = self.train_integrator(self.reg_odefunc.bound(self.odefunc), state, t, method=self.opt['method'],
+                                    options=options, atol=self.atol, rtol=self.rtol)
+        return out[0][1], tuple(r[1] for r in out[1:])
 
     def __repr__(self):
         return self.__class__.__name__ + '( Time Interval ' + str(self.t[0].item()) + ' -> ' + \

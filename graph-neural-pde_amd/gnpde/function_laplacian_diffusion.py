@@ -118,6 +118,11 @@ class LaplacianODEFunc(ODEFunc):
         w, _ = self._weights_tensor()
         return not w.requires_grad
 
+    def fixed_grid_reg_ok(self):
+        """The fused regularised solve (integrator._LaplacianRegFixedGridFn) writes out this class's
+        own Jacobian a (A - I): a subclass with another RHS keeps the per-RHS path."""
+        return type(self) is LaplacianODEFunc
+
     def adjoint_direct_ok(self, adjoint_params):
         """The adjoint's augmented RHS may be evaluated by K1 launches (integrator.
         _LaplacianAdjointFn, _laplacian_aug) when the weights are not an adjoint

@@ -715,6 +715,251 @@ class _LaplacianFixedGridFn(torch.autograd.Function):
         return gy, galpha, gbeta, None, None, None, None
 
 
+# --------------------------------------------------------------------------- regularised training path
+# the methods' weights beta_i: a regulariser state advances by dt * sum_i beta_i e(k_i) per step
+_REG_BETA = {'euler': (1.0,), 'midpoint': (0.0, 1.0), 'rk4': (0.125, 0.375, 0.375, 0.125)}
+
+
+def _reg_kinds(func):
+    """(kinds in the user's order) of a bound regularised RHS when every regulariser is one the
+    fused solve carries ('kinetic', 'directional', each at most once), else None."""
+    kinds = [getattr(fn, 'gnpde_reg_kind', None) for fn in getattr(func, 'regularization_fns', ())]
+    if not kinds or None in kinds or len(set(kinds)) != len(kinds):
+        return None
+    return tuple(kinds)
+
+
+def _reg_fused_ok(func, state, combine, grid_h, t_h, method):
+    """The fused regularised solve (_LaplacianRegFixedGridFn): the plain fused backward's
+    conditions on the integrated LaplacianODEFunc, euler or rk4, one output time (the block's
+    t = [0, T]), regularisers among quadratic_cost / directional_derivative, rows the row passes take."""
+    odefunc = getattr(func, 'odefunc', None)
+    ok = getattr(odefunc, 'fixed_grid_reg_ok', None)
+    if ok is None or not ok() or method not in ('euler', 'rk4') or len(t_h) != 2:
+        return False
+    if _reg_kinds(func) is None or state[0].dim() != 3 or state[0].shape[-1] > ops.ROW_MAX_COLS:
+        return False
+    if any(r.requires_grad or r.shape != state[0].shape[:-1] or r.dtype != torch.float32 for r in state[1:]):
+        return False
+    return _fused_backward_ok(odefunc, state[0], combine, grid_h, t_h)
+
+
+class _LaplacianRegFixedGridFn(torch.autograd.Function):
+    """_LaplacianFixedGridFn with the regulariser states r_j' = e_j(f) carried along (euler, rk4
+    3/8; one output time; the caller's node numbering):
+
+        kinetic      e(f) = 1/(2C) sum_c f^2
+        directional  d(f) = 1/(2C) sum_c v^2,  v = J^T f = a (A^T f - f),  J = a (A - I)
+
+    r' does not depend on r, so r_j(T) = sum_steps dt sum_i beta_i e_j(k_i) with the method's
+    weights beta and the stage derivatives k_i: what torchdiffeq computes on the tuple state.
+
+    Forward: the fused stage launches also store k_i (Stage.f_out); with the directional term one
+    transposed K1 launch per stage gives v_i; one ops.row_energy pass per step and regulariser reads
+    the step's k_i (v_i) once into an fp64 row accumulator, rounded to fp32 once at the end.  k_i
+    and v_i are kept for the backward beside the stage inputs.
+
+    Backward: the discrete adjoint of _LaplacianFixedGridFn with, for rho_j = dL/dr_j(T) [B,N],
+        gk_i += q_i,  q_i = (dt beta_i / C) (rho_1 (row-scale) k_i + J (rho_2 (row-scale) v_i))
+    (ops.row_axpy in place, and a K1 launch over the CSR whose epilogue adds J(.) in place), and
+        d alpha += a'(alpha) (2 / a) <rho_2, r_2(T)>        (0 when a = 0: then v = 0)
+    the explicit derivative of v = a (A^T - I) k with respect to a, summed over the stages; the
+    terms <u_i, x_i> and <gk_i, x0> follow from the enlarged gk_i.  rk4 writes gk_4 = dt/8 h with
+    h = g + q_4 / (dt/8) so that u_4 = dt/8 (A^T - I) h rides in the launches' epilogues as in the
+    unregularised adjoint; the other gk_i are formed against g (their q_i is added after the
+    epilogue that forms them)."""
+
+    @staticmethod
+    def forward(ctx, y0, alpha_train, beta_train, func, method, steps, kinds, *r0):
+        y = y0.detach().contiguous()
+        B, N, C = y.shape
+        R = B * N
+        o = laplacian_operands(func, y0, private_csc=True, snapshot=True)
+        directional = 'directional' in kinds
+        if directional:  # the CSR-order weights of J (.) in the backward: this node's own gather
+            o.w_csr = o.g.gather_weights(o.w.detach().float() if o.w.dtype != torch.float32 else o.w.detach())
+        acc = torch.zeros(len(kinds), R, dtype=torch.float64, device=y.device)
+        beta = _REG_BETA[method]
+        starts, stage_inputs, ks_all, vs_all = [], [], [], []
+        sol = torch.empty((2,) + tuple(y.shape), dtype=y.dtype, device=y.device)
+        sol[0].copy_(y)
+        for n_step, (ta, tb) in enumerate(steps):
+            dt = tb - ta
+            starts.append(y)
+            ks = [torch.empty_like(y) for _ in beta]
+            y1 = sol[1] if n_step == len(steps) - 1 else torch.empty_like(y)
+            if method == 'euler':
+                func.rhs_stage(ta, y, ops.Stage(f_out=ks[0], outs=[(y1, y, 1.0, dt, [])]))
+                stage_inputs.append([])
+            else:  # rk4 3/8 rule, the stage inputs as _fused_step forms them
+                x2, x3, x4 = (torch.empty_like(y) for _ in range(3))
+                func.rhs_stage(ta, y, ops.Stage(f_out=ks[0], outs=[(x2, y, 1.0, dt / 3.0, [])]))
+                func.rhs_stage(ta + dt / 3.0, x2, ops.Stage(f_out=ks[1], outs=[(x3, x2, -1.0, dt, [(y, 2.0)])]))
+                func.rhs_stage(ta + dt * 2.0 / 3.0, x3,
+                               ops.Stage(f_out=ks[2], outs=[(x4, x3, -1.0, dt, [(x2, 2.0)])]))
+                func.rhs_stage(tb, x4, ops.Stage(f_out=ks[3], outs=[(y1, x4, 0.375, dt * 0.125,
+                                                                      [(x3, 0.75), (y, -0.125)])]))
+                stage_inputs.append([x2, x3, x4])
+            coefs = [dt * b / (2.0 * C) for b in beta]
+            vs = None
+            if directional:
+                vs = [ops.spmm_rhs(o.g, o.w_csc, k, alpha=o.alpha, rhs=True, alpha_sigmoid=o.sig, transpose=True)
+                      for k in ks]
+            for j, kind in enumerate(kinds):
+                ops.row_energy(ks if kind == 'kinetic' else vs, coefs, acc=acc[j], accumulate=True)
+            ks_all.append(ks)
+            vs_all.append(vs)
+            y = y1
+        regs = tuple(torch.stack([r.detach(), r.detach() + acc[j].float().view(B, N)], 0) for j, r in enumerate(r0))
+        ctx.o, ctx.acc, ctx.kinds = o, acc, kinds
+        ctx.a_dev = torch.sigmoid(o.alpha) if o.sig else o.alpha
+        ctx.a_scale = ctx.a_dev.reshape(()).float().contiguous()
+        ctx.a_host = _host_scalar(ctx.a_dev)
+        ctx.func, ctx.method, ctx.steps = func, method, steps
+        ctx.starts, ctx.stage_inputs, ctx.ks, ctx.vs = starts, stage_inputs, ks_all, vs_all
+        return (sol,) + regs
+
+    @staticmethod
+    def backward(ctx, g_sol, *g_regs):
+        func, method, steps, kinds = ctx.func, ctx.method, ctx.steps, ctx.kinds
+        o = ctx.o
+        with torch.no_grad():
+            gr, w_csc, sig, add_source, x0 = o.g, o.w_csc, o.sig, o.add_source, o.x0
+            g_sol = g_sol.contiguous()
+            one = _device_one(g_sol.device)
+            a_dev, asc = ctx.a_dev, ctx.a_scale
+            B, N, C = ctx.starts[0].shape
+            rho = {kind: g_regs[j][1].contiguous().float() for j, kind in enumerate(kinds) if g_regs[j] is not None}
+            rho1, rho2 = rho.get('kinetic'), rho.get('directional')
+            beta = _REG_BETA[method]
+            acc64 = torch.zeros(2 + B * N, dtype=torch.float64, device=g_sol.device)
+            ga, gb, drow = acc64[0], acc64[1], acc64[2:]
+            T = dict(alpha=one, rhs=True, alpha_sigmoid=False, transpose=True)
+            e = lambda: torch.empty_like(g)  # noqa: E731
+
+            def add_q(gk, n, i, scale, base=None):
+                """gk = (base or gk) + scale * q_i of step n."""
+                dt = steps[n][1] - steps[n][0]
+                coef = scale * dt * beta[i] / C
+                if rho1 is not None:
+                    ops.row_axpy(gk if base is None else base, [(coef, rho1, ctx.ks[n][i])], out=gk)
+                elif base is not None:
+                    gk.copy_(base)
+                if rho2 is not None:
+                    tmp = ops.row_axpy(None, [(coef, rho2, ctx.vs[n][i])])
+                    ops.spmm_rhs(gr, o.w_csr, tmp, alpha=o.alpha, rhs=True, alpha_sigmoid=sig,
+                                 stage=ops.Stage(outs=[(gk, gk, 1.0, 1.0, [])]))
+
+            g = g_sol[1].clone()
+            a = ctx.a_host() if method != 'rk4' else None
+            for n in range(len(steps) - 1, -1, -1):
+                dt = steps[n][1] - steps[n][0]
+                y = ctx.starts[n]
+                if method == 'euler':
+                    gk = ops.rk_combine(None, [g], [dt], 1.0)
+                    add_q(gk, n, 0, 1.0)
+                    g_new = e()
+                    ops.spmm_rhs(gr, w_csc, gk, stage=ops.Stage(outs=[(g_new, g, 1.0, a, [])],
+                                                                dot=(y, drow, 1.0, True)), **T)
+                    if add_source:
+                        gb = gb + ops.dot(gk, x0)
+                    g = g_new
+                    continue
+                x2, x3, x4 = ctx.stage_inputs[n]
+                c8 = dt / 8.0
+                h, v, gk3, u3, gk2, gk1, acc, g_new = (e() for _ in range(8))
+                add_q(h, n, 3, 1.0 / c8, base=g)  # gk4 = c8 h
+                ops.spmm_rhs(gr, w_csc, h, stage=ops.Stage(f_out=v, outs=[(gk3, g, 3 * c8, dt * c8, [])],
+                                                           dot=(x4, drow, c8, True), scale=asc), **T)
+                add_q(gk3, n, 2, 1.0)
+                ops.spmm_rhs(gr, w_csc, gk3, stage=ops.Stage(f_out=u3, outs=[(gk2, g, 3 * c8, dt, [(v, -dt * c8)])],
+                                                             dot=(x3, drow, 1.0, True), scale=asc), **T)
+                add_q(gk2, n, 1, 1.0)
+                ops.spmm_rhs(gr, w_csc, gk2, stage=ops.Stage(outs=[
+                    (gk1, g, c8, dt / 3.0, [(v, dt * c8), (u3, -dt / 3.0)]),
+                    (acc, g, 1.0, 1.0, [(v, c8), (u3, 1.0)])], dot=(x2, drow, 1.0, True), scale=asc), **T)
+                add_q(gk1, n, 0, 1.0)
+                ops.spmm_rhs(gr, w_csc, gk1, stage=ops.Stage(outs=[(g_new, acc, 1.0, 1.0, [])],
+                                                             dot=(y, drow, 1.0, True), scale=asc), **T)
+                if add_source:
+                    gb = gb + c8 * ops.dot(h, x0) + ops.dot(gk3, x0) + ops.dot(gk2, x0) + ops.dot(gk1, x0)
+                g = g_new
+            ga = ops.sum_f64(drow, out=ga, accumulate=True)
+            if rho2 is not None:
+                # the explicit derivative of v = a (A^T - I) k to a: (2 / a) <rho_2, r_2(T)>, fp64
+                ex = ops.sum_f64(rho2.double().view(-1) * ctx.acc[kinds.index('directional')])
+                ad = a_dev.double()
+                ga = ga + torch.where(ad != 0, 2.0 * ex / torch.where(ad != 0, ad, torch.ones_like(ad)),
+                                      torch.zeros_like(ex))
+            g = g.add_(g_sol[0])
+            if sig:
+                ga = ga * (a_dev * (1 - a_dev)).double()
+        gy = g if ctx.needs_input_grad[0] else None
+        galpha = ga.to(func.alpha_train.dtype).reshape(func.alpha_train.shape) if ctx.needs_input_grad[1] else None
+        gbeta = gb.to(func.beta_train.dtype).reshape(func.beta_train.shape) \
+            if ctx.needs_input_grad[2] and add_source else None
+        return (gy, galpha, gbeta, None, None, None, None) + (None,) * len(kinds)
+
+
+class _TupleCombine(object):
+    """A stage combination applied to every component of a tuple state."""
+
+    def __init__(self, combine):
+        self.combine = combine
+
+    def __call__(self, y0, ks, coefs, scale):
+        return tuple(self.combine(y0[i], [k[i] for k in ks], coefs, scale) for i in range(len(y0)))
+
+
+def _odeint_tuple(func, state, t, method, options, combine):
+    """odeint over a tuple state (the regularised RHS: (x, r_1, ...)), torchdiffeq's convention: a
+    tuple of [len(t), ...] tensors.  Fixed-grid methods only: the fused regularised solve when it
+    applies (_reg_fused_ok), else autograd through every RHS call and stage combination."""
+    if method in ADAPTIVE_METHODS:
+        raise NotImplementedError("gnpde.odeint: a tuple state (ODE regularisers) under the adaptive method %r "
+                                  "is out of scope; use one of %s" % (method, ', '.join(FIXED_METHODS)))
+    if method in MULTISTEP_METHODS:
+        raise NotImplementedError("gnpde.odeint: a tuple state (ODE regularisers) under the multistep method %r "
+                                  "is out of scope; use one of %s" % (method, ', '.join(FIXED_METHODS)))
+    if method not in FIXED_METHODS:
+        raise NotImplementedError("gnpde.odeint: method %r not supported" % method)
+    if len(state) < 1 or not all(isinstance(s, torch.Tensor) for s in state):
+        raise ValueError("gnpde.odeint: a tuple state holds tensors")
+    if any(s.dtype == torch.bfloat16 for s in state):
+        raise NotImplementedError("gnpde.odeint: a tuple state (ODE regularisers) with a bf16 state is out of "
+                                  "scope: the regulariser passes are fp32")
+    if combine is None:
+        if not state[0].is_cuda:
+            raise RuntimeError("gnpde.odeint: y0 must be a ROCm device tensor (stage combinations run in HIP)")
+        combine = _Combine()
+    t_h = _host_times(t)
+    grid_h = _host_grid(t_h, t.dtype, options.get('step_size'))
+    if not (grid_h[0] == t_h[0] and grid_h[-1] == t_h[-1]):
+        raise AssertionError("time grid does not cover t")
+    steps = list(zip(grid_h[:-1], grid_h[1:]))
+    if _reg_fused_ok(func, state, combine, grid_h, t_h, method) and \
+            _nfe_headroom(func.odefunc, len(steps) * RHS_PER_STEP[method]):
+        odeint.last_reg_path = 'fused'
+        f = func.odefunc
+        return _LaplacianRegFixedGridFn.apply(state[0], f.alpha_train, f.beta_train, f, method, steps,
+                                              _reg_kinds(func), *state[1:])
+    odeint.last_reg_path = 'restated'
+    tc = _TupleCombine(combine)
+    solution = [state]
+    j = 1
+    yc = state
+    for ta, tb in steps:
+        y1 = _fixed_step(method, func, ta, tb - ta, tb, yc, tc)
+        while j < len(t_h) and tb >= t_h[j]:
+            solution.append(tuple(_linear_interp(ta, tb, a, b, t_h[j]) for a, b in zip(yc, y1)))
+            j += 1
+        yc = y1
+    while j < len(t_h):
+        solution.append(yc)
+        j += 1
+    return tuple(torch.stack([s[i] for s in solution], 0) for i in range(len(state)))
+
+
 def _host_scalar(v):
     """A device scalar's value for the host later: an asynchronous copy into pinned
     memory behind an event; the returned callable waits for that event only (not
@@ -2044,6 +2289,12 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, combine
     """torchdiffeq.odeint(func, y0, t, rtol, atol, method, options) -> [len(t), *y0.shape]."""
     method = method or 'dopri5'
     options = dict(options or {})
+    if isinstance(y0, (tuple, list)):  # the regularised RHS's state (gnpde.regularized_ODE_function)
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(t)
+        if t.dim() != 1 or len(t) < 2:
+            raise ValueError("t must be a 1-D tensor with at least two time points")
+        return _odeint_tuple(func, tuple(y0), t, method, options, combine)
     if combine is None:
         if not y0.is_cuda:
             raise RuntimeError("gnpde.odeint: y0 must be a ROCm device tensor (stage combinations run in HIP)")
@@ -2097,6 +2348,7 @@ odeint.last_path = None
 odeint.last_adams = None  # the last multistep solve: per-step corrector 'iterations', 'converged', and 'ratios'
 odeint.last_capped = False  # whether it stopped at options['gnpde_max_attempts'] before the output time
 odeint.last_dense_fold = False  # whether its dense output was folded into the steps (DENSE_FOLD)
+odeint.last_reg_path = None  # the last tuple-state (regularised) solve: 'fused' or 'restated'
 
 
 # --------------------------------------------------------------------------- adjoint
@@ -2398,6 +2650,9 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     (as in torchdiffeq, not other tensors the RHS closes over).  ``combine``: odeint's
     (the host tests inject _torch_combine for CPU tensors; None: the HIP stage combinations)."""
     method = method or 'dopri5'
+    if isinstance(y0, (tuple, list)):
+        raise NotImplementedError("gnpde.odeint_adjoint: a tuple state (ODE regularisers with adjoint=True) is out "
+                                  "of scope; train regularised solves with odeint (opt['adjoint'] = False)")
     if adjoint_params is None:
         adjoint_params = tuple(p for p in func.parameters() if p.requires_grad)
     adjoint_params = tuple(adjoint_params)

@@ -2182,6 +2182,113 @@ def rk_combine(y0, ks, coefs, scale, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- regulariser row passes
+ROW_MAX_ARRAYS = 4  # arrays of one gnpde_row_energy_f32 pass
+ROW_MAX_COLS = 256  # row length the regulariser passes take
+
+
+def _row_arrays(ks, name):
+    """Contiguous fp32 device arrays of one shape [..., C] -> (list, R, C)."""
+    ks = [k.contiguous() for k in ks]
+    for j, k in enumerate(ks):
+        _require_gpu(k, "%s[%d]" % (name, j), torch.float32)
+        if k.shape != ks[0].shape or k.dim() < 1:
+            raise ValueError("%s: arrays must share one shape [..., C]" % name)
+    C = ks[0].shape[-1]
+    return ks, ks[0].numel() // max(C, 1), C
+
+
+def row_energy_torch(ks, coefs, acc=None, accumulate=False):
+    """The row pass of ``row_energy`` restated in torch (any device): fp64
+    s[r] = sum_i coefs[i] * sum_c ks[i][r,c]^2 over the leading dims' rows.  Returns the fp32
+    rounding of s shaped like the leading dims, or, with ``acc`` (fp64, one entry per row), stores
+    (or, with accumulate, adds) s there and returns ``acc``."""
+    s = None
+    for k, c in zip(ks, coefs):
+        e = float(c) * k.double().pow(2).sum(-1)
+        s = e if s is None else s + e
+    if acc is None:
+        return s.float()
+    if accumulate:
+        acc.add_(s.view(acc.shape))
+    else:
+        acc.copy_(s.view(acc.shape))
+    return acc
+
+
+def row_energy(ks, coefs, acc=None, accumulate=False):
+    """s[r] = sum_i coefs[i] * sum_c ks[i][r,c]^2 in one read of up to 4 fp32 arrays [..., C]
+    (gnpde_row_energy_f32: the per-row sum in fp64, a fixed order, no atomics).  Without ``acc``
+    returns the fp32 rounding shaped like the leading dims; with ``acc`` (fp64 device tensor, one
+    entry per row) stores s there, or adds it with accumulate=True, and returns ``acc``."""
+    if not 1 <= len(ks) <= ROW_MAX_ARRAYS or len(coefs) != len(ks):
+        raise ValueError("row_energy: 1 to %d arrays and one coefficient each" % ROW_MAX_ARRAYS)
+    ks, R, C = _row_arrays(ks, "row_energy")
+    if not 1 <= C <= ROW_MAX_COLS:
+        raise ValueError("row_energy: rows of 1 to %d columns (got %d)" % (ROW_MAX_COLS, C))
+    dev = ks[0].device
+    n = len(ks)
+    kp = (ctypes.c_void_p * n)(*[k.data_ptr() for k in ks])
+    cf = (ctypes.c_double * n)(*[float(c) for c in coefs])
+    out = None
+    if acc is None:
+        out = torch.empty(ks[0].shape[:-1], dtype=torch.float32, device=dev)
+    else:
+        _require_gpu(acc, "row_energy acc", torch.float64)
+        if not acc.is_contiguous() or acc.numel() != R:
+            raise ValueError("row_energy: acc must be contiguous with one fp64 per row")
+    _lib.call("gnpde_row_energy_f32", R, C, n, kp, cf, _ptr(acc), int(bool(accumulate)), _ptr(out), _stream(dev))
+    return out if acc is None else acc
+
+
+def row_axpy_torch(base, terms, out=None):
+    """``row_axpy`` restated in torch (any device): base + sum_j coef_j * g_j[..., None] * src_j,
+    formed in fp64 and rounded to fp32 once; terms = [(coef, g, src), ...]."""
+    src0 = terms[0][2] if terms else base
+    s = torch.zeros(src0.shape, dtype=torch.float64, device=src0.device) if base is None else base.double()
+    for c, g, src in terms:
+        s = s + (float(c) * g.double()).reshape(src.shape[:-1]).unsqueeze(-1) * src.double()
+    s = s.float()
+    if out is not None:
+        out.copy_(s)
+        return out
+    return s
+
+
+def row_axpy(base, terms, out=None):
+    """out[r,:] = base[r,:] + sum_j coef_j * g_j[r] * src_j[r,:] in one pass (gnpde_row_axpy_f32):
+    terms = [(coef, g, src), ...], at most two; g_j one value per row, all fp32 or all fp64;
+    ``base`` None = 0; ``out`` may be ``base`` (default: a new tensor).  Every element is an fp64
+    sum rounded to fp32 once."""
+    if len(terms) > 2 or (base is None and not terms):
+        raise ValueError("row_axpy: a base and/or one or two terms")
+    srcs, R, C = _row_arrays([s for _, _, s in terms] + ([base] if base is not None else []), "row_axpy")
+    if not 1 <= C <= ROW_MAX_COLS:
+        raise ValueError("row_axpy: rows of 1 to %d columns (got %d)" % (ROW_MAX_COLS, C))
+    base_c = srcs.pop() if base is not None else None
+    if out is base and base is not None and base_c is not base:
+        raise ValueError("row_axpy: an in-place base must be contiguous")
+    dev = srcs[0].device if srcs else base_c.device
+    gs = [g.contiguous() for _, g, _ in terms]
+    g_f64 = bool(gs) and gs[0].dtype == torch.float64
+    for g in gs:
+        _require_gpu(g, "row_axpy g", torch.float64 if g_f64 else torch.float32)
+        if g.numel() != R:
+            raise ValueError("row_axpy: g must hold one value per row")
+    if out is None:
+        out = torch.empty_like(srcs[0] if srcs else base_c)
+    else:
+        _require_gpu(out, "row_axpy out", torch.float32)
+        if not out.is_contiguous() or out.numel() != R * C:
+            raise ValueError("row_axpy: out must be contiguous and sized like the arrays")
+    n = len(terms)
+    sp = (ctypes.c_void_p * max(n, 1))(*[s.data_ptr() for s in srcs])
+    gp = (ctypes.c_void_p * max(n, 1))(*[g.data_ptr() for g in gs])
+    cf = (ctypes.c_double * max(n, 1))(*[float(c) for c, _, _ in terms])
+    _lib.call("gnpde_row_axpy_f32", R, C, _ptr(base_c), n, sp, gp, int(g_f64), cf, _ptr(out), _stream(dev))
+    return out
+
+
 # --------------------------------------------------------------------------- multistep (Adams) passes
 def _adams_operand(t, name, like):
     _require_gpu(t, name, torch.float32)

@@ -697,6 +697,24 @@ int gnpde_edge_attention_csr_f32(const int32_t* rowidx, const int32_t* col, int6
 int gnpde_rk_combine_f32(int64_t n, const float* y0, int nk, const float* const* ks, const double* coef,
                          double scale, float* out, void* stream);
 
+/* The row passes of the ODE regularisers (gnpde.regularized_ODE_function; entry points
+ * added under ABI 8).  Arrays are [R, C] fp32, contiguous, 1 <= C <= 256; a team of lanes
+ * of one wavefront owns a row (64 / L short rows per wavefront), 16-byte accesses when
+ * C % 4 == 0 and every base is 16-byte aligned, a scalar form otherwise.  No atomics, a
+ * fixed summation order per row: the same bits whatever the grid.
+ *
+ *   s[r] = sum_{i<n} coef[i] * sum_c ks[i][r,c]^2      (1 <= n <= 4; carried in fp64)
+ *   acc (may be NULL): acc[r] = s[r], or acc[r] += s[r] with accumulate != 0 (fp64: the
+ *       running regulariser state of a fused solve);
+ *   out (may be NULL): out[r] = (float)s[r] (the per-RHS value).  One of the two at least. */
+int gnpde_row_energy_f32(int64_t R, int64_t C, int n, const float* const* ks, const double* coef, double* acc,
+                         int accumulate, float* out, void* stream);
+/*   out[r,:] = base[r,:] + sum_{j<n} coef[j] * g[j][r] * src[j][r,:]     (0 <= n <= 2)
+ * base may be NULL (= 0) and may be out itself; g[j] are [R], fp64 when g_f64 != 0, else
+ * fp32.  Every element is an fp64 sum rounded to fp32 once.                              */
+int gnpde_row_axpy_f32(int64_t R, int64_t C, const float* base, int n, const float* const* src,
+                       const void* const* g, int g_f64, const double* coef, float* out, void* stream);
+
 /* Entry of a solve (gnpde.integrator): dst[k] = src[order[k]] for k < rows
  * (order NULL: identity), rows of row_bytes bytes (a multiple of 16, 16-byte
  * aligned pointers); dst_copy (may be NULL) receives src unchanged,
